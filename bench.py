@@ -9,6 +9,11 @@ One "step" = the reference train_step (models/simclr.py:86-95) on one per-GPU ba
 ResNet-50 (std 7x7/2 stem) + projector forward with per-view BatchNorm -> NT-Xent over the GLOBAL batch
 (RCCL all-gather of the embeddings) -> backward -> gradient all-reduce -> SGD-Nesterov -> loss.item().
 Inputs are synthetic and resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds everything else the line can carry, each
+after the timed region: the per-kernel-class roofline, the arithmetic block and the fp32-instruction leg, config 3's per-rank emulation, the
+collective timing of a multi-rank run, the CPU baseline with its parity gates, config 1, the kNN leg and the BYOL / DINO legs.
+``--dump-outputs DIR`` writes what the last timed step left its caller (loss, parameters) as .npy files: builds compare output for output.
 """
 import argparse
 import json
@@ -814,6 +819,21 @@ def other_config_leg(device, algo, tf, source, sample_ids, rows, cfg, warmup=3, 
     return out
 
 
+DUMP_PARAMS_MAX = 1 << 23         # float32 elements of the parameter sample: 32 MB, inside the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, loss, trainer):
+    """``--dump-outputs DIR``: what the last timed step handed its caller - the loss (loss.npy, float64 [1]) and the parameters the update
+    left (params.npy, float32: the optimizer's flat parameter buffer, every k-th element with the smallest k that keeps it to DUMP_PARAMS_MAX
+    elements - a fixed sample, the same on every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = trainer.optim.arena.data
+    stride = -(-flat.numel() // DUMP_PARAMS_MAX)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "params.npy"), flat[::stride].detach().float().cpu().numpy())
+
+
 def config1_child(argv):
     """``bench.py --config1-child BATCH STEPS``: the HIP side of config_1's block, alone in this process; one JSON line on stdout."""
     from ssv_amd import _lib
@@ -840,6 +860,11 @@ def main():
                     "(ssv_amd.distributed.emulate_world: every data-parallel code path, transport replaced by device copies)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the config3_rank_emulation / other_configs (BYOL, DINO) legs of the default line")
     ap.add_argument("--no-arith-legs", action="store_true", help="skip the arithmetic block and the fp32-instruction leg (profiling runs: only the shipped step's kernels in the trace)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline, after the timed region: roofline, arithmetic and fp32-instruction "
+                    "legs, config-3 emulation, collective timing, CPU baseline and parity gates, config 1, kNN and BYOL / DINO legs (the --no-* switches "
+                    "and --prof-steps trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's loss and a fixed sample of the parameters it "
+                    "left as DIR/{loss,params}.npy (rank 0)")
     args = ap.parse_args()
 
     from ssv_amd import _lib, distributed as hdist
@@ -890,19 +915,23 @@ def main():
         loss = step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, train_step.trainer)
     dist_info = None
     if world > 1:
         import torch.distributed as dist
         per_rank = [None] * world
         dist.all_gather_object(per_rank, float(dt))
         dt = max(per_rank)                                         # MAX over ranks: the step is as slow as its slowest rank
-        # what the exchange costs: extra steps (after the timed region) with an event pair around every collective, on the stream it runs on
-        hdist.comm_timing(True)
-        for _ in range(2):
-            step()
-        torch.cuda.synchronize()
-        comms = [None] * world
-        dist.all_gather_object(comms, hdist.comm_timing(False) / 2)
+        comms = None
+        if args.full:
+            # what the exchange costs: extra steps (after the timed region) with an event pair around every collective, on the stream it runs on
+            hdist.comm_timing(True)
+            for _ in range(2):
+                step()
+            torch.cuda.synchronize()
+            comms = [None] * world
+            dist.all_gather_object(comms, hdist.comm_timing(False) / 2)
         sync = getattr(train_step.trainer.optim, "grad_sync", None)
         props = torch.cuda.get_device_properties(device)
         mine_dev = {"rank": rank, "local_rank": int(os.environ.get("LOCAL_RANK", "0")), "pid": os.getpid(), "device": device.index, "name": props.name,
@@ -913,7 +942,7 @@ def main():
                      "launched_by": "bench.py (ssv_amd.launch: child torch.distributed.run)" if os.environ.get("SSV_LAUNCHED_BY") else "outer launcher",
                      "devices": devices,
                      "ms_per_step_min_over_ranks": round(min(per_rank) / args.steps * 1e3, 3), "ms_per_step_max_over_ranks": round(max(per_rank) / args.steps * 1e3, 3),
-                     "comm_ms_per_step": round(max(comms), 3),
+                     "comm_ms_per_step": None if comms is None else round(max(comms), 3),
                      "comm_note": "device time between HIP events around every collective (embedding / LSE all-gathers, per-bucket gradient all-reduces on the "
                                   "exchange stream), max over ranks, 2 extra steps; the bucketed all-reduces overlap the backward pass, so this is not additive to ms_per_step",
                      "gradient_buckets": None if sync is None else [[n, (hi - lo) * 4] for n, lo, hi in sync.buckets]}
@@ -928,7 +957,7 @@ def main():
         conv_flop_step, algo_bytes_step = step_work(args.algo, s, s, b)       # per GPU and step; 2 FLOP/MAC
         attn_flop_step = 0.0
     roof, classes = None, {}
-    if args.prof_steps > 0:
+    if args.full and args.prof_steps > 0:
         # per-kernel durations are only meaningful when kernels do not overlap: the instrumented steps run the two
         # views back to back on ONE stream (the timed region above runs them on two streams)
         was_dual = hnn.set_view_streams(False)
@@ -1051,7 +1080,7 @@ def main():
 
     # ---- the same step on the fp32 MFMA instruction, and what the shipped arithmetic is (rank 0, one GPU: after the timed region) ----
     fp32_leg, arith = None, None
-    if rank == 0 and world == 1 and not args.emulate_world and not args.no_arith_legs:
+    if args.full and rank == 0 and world == 1 and not args.emulate_world and not args.no_arith_legs:
         from ssv_amd import ops as _ops
         try:
             arith = arithmetic_block(device)
@@ -1062,7 +1091,7 @@ def main():
 
     # ---- BASELINE config 3's per-rank step on this one GPU (default SimCLR line only; after the timed region and the instrumented steps) ----
     emu_block = None
-    legs = rank == 0 and world == 1 and args.algo == "simclr" and not args.emulate_world and not args.no_other_configs
+    legs = args.full and rank == 0 and world == 1 and args.algo == "simclr" and not args.emulate_world and not args.no_other_configs
     if legs:
         try:
             emu_block = config3_rank_emulation(device, train_step, step, b, ms_per_step)
@@ -1072,7 +1101,7 @@ def main():
     if args.emulate_world > 1:                                         # --emulate-world W: the whole line IS one rank's step of the W-rank job
         emu_self = {"emulated_world": args.emulate_world, "rank": 0, "global_batch": b * args.emulate_world,
                     "value_is": "images/sec of ONE rank's step (per-rank batch / step time); the W-rank job with free transport would run W x that",
-                    "ntxent": time_ntxent(device, b * args.emulate_world, b) if args.algo == "simclr" else None,
+                    "ntxent": time_ntxent(device, b * args.emulate_world, b) if args.full and args.algo == "simclr" else None,
                     "gradient_buckets": [[n, (hi - lo) * 4] for n, lo, hi in train_step.trainer.optim.grad_sync.buckets],
                     "transport": "emulated (ssv_amd.distributed.emulate_world): all-gather = one device copy of the gathered size with this rank's block in "
                                  "every slot, all-reduce(SUM) = x world on the exchange stream; every kernel of the rank's step is the real one"}
@@ -1107,7 +1136,7 @@ def main():
         out["config3_rank_emulation"] = emu_block
     del step, train_step                                               # the extra legs below build their own trainers
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.algo == "dino":
             out["cpu_baseline"], dino_cpu_losses = cpu_baseline_dino()
             out["parity_gate"] = parity_gate_dino(device, dino_cpu_losses)

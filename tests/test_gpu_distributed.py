@@ -380,7 +380,7 @@ def test_bench_gpus_2_starts_its_two_ranks_itself():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16",
-                          "--no-cpu-baseline", "--prof-steps", "0"], env=_plain_env(SSV_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--prof-steps", "0", "--full"], env=_plain_env(SSV_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines                                        # ONE line, from rank 0

@@ -118,7 +118,7 @@ def test_full_size_augmentation_is_shard_invariant(dev):
 
 
 def test_the_drivers_default_bench_command_carries_every_block_of_the_line():
-    """`python bench.py` as the driver runs it (single GPU, no flags but a small batch / image so that the test takes a minute): ONE JSON line with the headline
+    """`python bench.py --full` (single GPU, no other flags but a small batch / image so that the test takes a minute): ONE JSON line with the headline
     fields, `roofline`, `cpu_baseline`, `parity_gate` (teacher-forced pass, the batch-512 kernel selection recorded), `config1` (step graph beside the eager step),
     `config3_rank_emulation` (one rank of eight, emulated) and `other_configs.{byol, dino}` - every extra leg without an error string; and `--emulate-world 8`."""
     import json
@@ -129,7 +129,8 @@ def test_the_drivers_default_bench_command_carries_every_block_of_the_line():
     env = dict(os.environ, WANDB_MODE="disabled")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "SSV_DIST_FORCE"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "32", "--size", "64", "--prof-steps", "1"],
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "32", "--size", "64", "--prof-steps", "1",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=1200)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -155,3 +156,37 @@ def test_the_drivers_default_bench_command_carries_every_block_of_the_line():
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert out["emulated_world"]["emulated_world"] == 8 and out["emulated_world"]["global_batch"] == 256 and len(out["emulated_world"]["gradient_buckets"]) >= 5
+
+
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_steps_outputs(tmp_path):
+    """`python bench.py` without --full: the headline fields only (no extra leg runs), `steps` timed steps, and --dump-outputs writes the last
+    timed step's loss (float64) and a fixed sample of the parameters it left (float32), together at most 64 MB; two runs with the same arguments
+    write the same loss."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, WANDB_MODE="disabled")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "SSV_DIST_FORCE"):
+        env.pop(k, None)
+    losses = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32", "--size", "64",
+                              "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+        assert abs(out["value"] - 32 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-3
+        for key in ("roofline", "arithmetic", "fp32_mfma_instruction_path", "cpu_baseline", "parity_gate"):
+            assert out[key] is None, key
+        for key in ("config1", "config3_rank_emulation", "other_configs", "eval_knn"):
+            assert key not in out, key
+        loss, params = np.load(tmp_path / run / "loss.npy"), np.load(tmp_path / run / "params.npy")
+        assert loss.dtype == np.float64 and loss.shape == (1,) and loss[0] == out["config"]["last_loss"]
+        assert params.dtype == np.float32 and params.ndim == 1 and np.isfinite(params).all() and np.abs(params).max() > 0
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 64 << 20
+        losses.append(float(loss[0]))
+    assert abs(losses[0] - losses[1]) <= 1e-4 * abs(losses[0])

@@ -95,6 +95,24 @@ def test_bench_replays_counters_only_with_their_build_identity(tmp_path):
         assert rel is not None and src and len(src) == 16, fname
 
 
+def test_bench_dump_outputs_writes_loss_and_a_bounded_parameter_sample(tmp_path):
+    """bench.py --dump-outputs: loss.npy (float64 [1]) and params.npy (float32, every k-th element of the flat parameter buffer, at most
+    DUMP_PARAMS_MAX elements, the same sample on every call) - a ResNet-50-sized buffer stays inside 64 MB."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    flat = torch.arange(28_000_003, dtype=torch.float32)
+    trainer = types.SimpleNamespace(optim=types.SimpleNamespace(arena=types.SimpleNamespace(data=flat)))
+    bench.dump_outputs(str(tmp_path / "d"), 4.25, trainer)
+    loss, params = np.load(tmp_path / "d" / "loss.npy"), np.load(tmp_path / "d" / "params.npy")
+    assert loss.dtype == np.float64 and loss.tolist() == [4.25]
+    assert params.dtype == np.float32 and len(params) <= bench.DUMP_PARAMS_MAX and params[0] == 0.0
+    np.testing.assert_array_equal(params, flat[::4].numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "d").iterdir()) <= 64 << 20
+
+
 def test_committed_counters_were_measured_on_the_current_sources():
     """The build identity is the sha256 over the kernel sources in link order + the two headers + the compile flags (csrc/Makefile: SRC_SHA).  When the sources have moved on since the
     counters under profiles/ were measured, bench.py prints `counters_stale: true` - this test then SKIPS with the reason (a reminder to re-run tools/profile_step.sh
