@@ -1997,8 +1997,14 @@ namespace {
 
 // Does a forward-kernel launch described by d run its bf16-piece variant (SSV_ARITH_BF16X3)?  The float4 path with whole 32-channel k-tiles, 16-byte output rows, a
 // pre-split weight operand (a block-diagonal bank included: its tiles contract over their own groups' channels in either arithmetic).
+// The kernels address the three planes with 32-bit byte offsets (plane q at q * 2 K R S C) and OOB_OFF = 2^31 as their zero-fill sentinel: a weight of
+// 6 K R S C >= 2^31 bytes of planes would wrap them (check_desc admits K R S C up to 2^29) - such a launch runs on fp32 MFMA.
+inline bool sp_planes_fit(const ssv_conv_desc* d) {
+  return (int64_t)d->K * d->R * d->S * d->C * 6 < (1ll << 31);
+}
 inline bool sp_fwd_ok(const ssv_conv_desc* d, int groups = 0) {
-  return d->arithmetic == SSV_ARITH_BF16X3 && d->w_planes != nullptr && (((uintptr_t)d->w_planes) & 15) == 0 && d->C % 32 == 0 && d->K % 4 == 0;
+  return d->arithmetic == SSV_ARITH_BF16X3 && d->w_planes != nullptr && (((uintptr_t)d->w_planes) & 15) == 0 && d->C % 32 == 0 && d->K % 4 == 0 &&
+         sp_planes_fit(d);
 }
 // ... and with how many accumulators per tile: one up to a contraction of SP_DUAL_FROM products per output, two beyond (a property of the LAYER - every fused and
 // unfused variant of a layer takes the same form, so they stay bit-identical).  Measured on the 53 ResNet-50 layers (tests/test_gpu_split.py): with one accumulator
@@ -2010,7 +2016,8 @@ inline int sp_fwd_mode(const ssv_conv_desc* d, int groups = 0) {
 }
 // the strided data-gradient kernel: its 128 x 128 tile (C >= 128), whole 32-channel k-tiles of the output channels, the weights pre-split
 inline bool sp_dgrad_ok(const ssv_conv_desc* d) {
-  return d->arithmetic == SSV_ARITH_BF16X3 && d->w_planes != nullptr && (((uintptr_t)d->w_planes) & 15) == 0 && d->K % 32 == 0 && d->C >= 128 && d->C % 8 == 0;
+  return d->arithmetic == SSV_ARITH_BF16X3 && d->w_planes != nullptr && (((uintptr_t)d->w_planes) & 15) == 0 && d->K % 32 == 0 && d->C >= 128 && d->C % 8 == 0 &&
+         sp_planes_fit(d);
 }
 inline bool sp_wgrad_ok(const ssv_conv_desc* d, int groups = 0) {
   return d->arithmetic == SSV_ARITH_BF16X3 && d->C % 4 == 0 && d->K % 4 == 0;

@@ -24,8 +24,8 @@ lib = C.CDLL(lib_path)
 TYPES = {"void_p": C.c_void_p, "i32": C.c_int32, "i64": C.c_int64, "f32": C.c_float, "f64": C.c_double, "u64": C.c_uint64, "size": C.c_size_t,
          "int": C.c_int, "char_p": C.c_char_p}
 
-class ConvDesc(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "C", "K", "R", "S", "stride", "pad", "Ho", "Wo")]
+class ConvDesc(C.Structure):                     # ABI 120: 13 int32 fields, then the pre-split weight planes
+    _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "C", "K", "R", "S", "stride", "pad", "Ho", "Wo", "arithmetic", "reserved")] + [("w_planes", C.c_void_p)]
 class AugCfg(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("brightness", "contrast", "saturation", "hue", "p_jitter", "p_gray", "p_flip", "scale_min", "scale_max", "ratio_min", "ratio_max")]
 class BnGate(C.Structure):
@@ -61,6 +61,17 @@ def build(kind, mode):
     return PTR[kind]() if mode == "null" else C.cast(hp, PTR[kind])
 
 out = {}
+# CONSISTENT descriptors that reach ssv_conv_arithmetic, so that `arithmetic` and `w_planes` are read (under ASan / UBSan in the sanitizer run):
+# products 0 / 1 / 2 and an invalid one, arithmetic 0 / 6, w_planes NULL / misaligned / aligned (never dereferenced by host code)
+arith = lib.ssv_conv_arithmetic
+arith.restype, arith.argtypes = C.c_int, [C.POINTER(ConvDesc), C.c_int32]
+probes = []
+for arithmetic in (0, 6):
+    for planes in (None, hp + 8, hp):
+        for product in (0, 1, 2, 3, -1):
+            d = ConvDesc(2, 8, 8, 128, 64, 3, 3, 1, 1, 8, 8, arithmetic, 0, planes)
+            probes.append([arithmetic, -1 if planes is None else planes - hp, product, arith(C.byref(d), product)])
+out_probes = probes
 for name, (res, args) in sorted(sigs.items()):
     fn = getattr(lib, name)
     fn.restype = TYPES[res]
@@ -74,7 +85,7 @@ for name, (res, args) in sorted(sigs.items()):
     out[name] = got
 err = lib.ssv_last_error
 err.restype = C.c_char_p
-print("RESULT " + json.dumps({"calls": out, "last_error": err().decode()}))
+print("RESULT " + json.dumps({"calls": out, "last_error": err().decode(), "sizeof_desc": C.sizeof(ConvDesc), "arith_probes": out_probes}))
 '''
 
 _KIND = {C.c_void_p: "void_p", C.c_int32: "i32", C.c_int64: "i64", C.c_float: "f32", C.c_double: "f64", C.c_uint64: "u64", C.c_size_t: "size",
@@ -127,6 +138,21 @@ def _check(result):
             bad.append((name, "accepted a negative dimension", got))
     assert not bad, "\n".join(f"{n}: {why} {g}" for n, why, g in bad)
     assert result["last_error"], "ssv_last_error() must describe the last refusal"
+    from ssv_amd import _lib
+    assert len(result["arith_probes"]) == 30
+    assert result["sizeof_desc"] == C.sizeof(_lib.ConvDesc), "the driver's ssv_conv_desc is not the ABI's"
+    # ssv_conv_arithmetic on a consistent 3x3 / C = 128 / K = 64 descriptor: bf16x3 only when asked for; the forward and data-gradient products also need
+    # 16-byte-aligned planes; the weight gradient ignores them; an invalid product is refused
+    for arithmetic, planes_off, product, got in result["arith_probes"]:
+        if product not in (0, 1, 2):
+            exp = -1
+        elif arithmetic != 6:
+            exp = 0
+        elif product == 2:
+            exp = 6
+        else:
+            exp = 6 if planes_off == 0 else 0        # planes_off 0: aligned, 8: misaligned, -1: NULL
+        assert got == exp, (arithmetic, planes_off, product, got, exp)
 
 
 def test_every_entry_point_refuses_bad_arguments(tmp_path):

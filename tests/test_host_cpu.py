@@ -333,3 +333,30 @@ def test_step_graph_lifetime_rules():
     graph._LIVE.add(strong)
     graph._close_all()
     assert strong.graphs == {}
+
+
+def test_conv_arithmetic_falls_back_to_fp32_when_the_weight_planes_pass_2_gib():
+    """The bf16-piece kernels address a weight's three planes with 32-bit byte offsets (6 K R S C bytes of planes, OOB_OFF = 2^31 as the zero-fill
+    sentinel) while check_desc admits K R S C up to 2^29: from 6 K R S C >= 2^31 the forward and the strided data gradient must report (and take)
+    fp32 MFMA.  The planes pointer is a fake 16-byte-aligned address: ssv_conv_arithmetic never dereferences it."""
+    import ctypes as C
+    from ssv_amd import _lib
+    lib = _lib.load()
+
+    def arith(n, h, c, k, r, stride, product):
+        pad = 0
+        ho = (h - r) // stride + 1
+        d = _lib.ConvDesc(n, h, h, c, k, r, r, stride, pad, ho, ho)
+        d.arithmetic, d.w_planes = _lib.ARITH_BF16X3, 1 << 20
+        return lib.ssv_conv_arithmetic(C.byref(d), product)
+
+    limit = (1 << 31) // 6                                   # K R S C of the largest weight whose planes fit: 357,913,941
+    assert 21824 * 16384 <= limit < 22528 * 16384
+    for product, stride in ((0, 1), (1, 2)):
+        assert arith(8 if product == 0 else 1, 1 if product == 0 else 4, 16384, 21824, 1, stride, product) == _lib.ARITH_BF16X3
+        assert arith(8 if product == 0 else 1, 1 if product == 0 else 4, 16384, 22528, 1, stride, product) == _lib.ARITH_F32_MFMA
+    # the limit counts K R S C, not K C alone: a 3x3 layer with K = 22,016 and C = 1,792 (355,074,048) keeps bf16x3, with C = 1,824 (361,414,656) it does not
+    assert arith(1, 3, 1792, 22016, 3, 1, 0) == _lib.ARITH_BF16X3
+    assert arith(1, 3, 1824, 22016, 3, 1, 0) == _lib.ARITH_F32_MFMA
+    # the weight gradient has no pre-split operand: its form does not depend on the weight's size
+    assert arith(8, 1, 16384, 22528, 1, 1, 2) == _lib.ARITH_BF16X3
