@@ -30,63 +30,13 @@
 #include <string.h>
 #include <type_traits>
 
-// Compile-time switches of DIAGNOSTIC builds only (tools/probe/build_variant.sh builds a side library with them; the shipped Makefile defines
-// none, and nothing here reads the environment): the what-ifs and A/Bs they served are tabulated in profiles/r02_experiments_step_time.txt.
-#ifndef SSV_EXP_LDS_PAD
-#define SSV_EXP_LDS_PAD 0   // diagnostic builds only: extra LDS floats per forward / data-gradient workgroup (forces a lower occupancy)
-#endif
-#ifdef SSV_CONV_VGPR          // diagnostic builds only: register cap of the forward / data-gradient kernels (amdgpu_num_vgpr(n) caps the unified file at 2n)
-#define SSV_CONV_ATTR __attribute__((amdgpu_num_vgpr(SSV_CONV_VGPR)))
-#else
-#define SSV_CONV_ATTR
-#endif
-#ifndef SSV_WHATIF
-#define SSV_WHATIF 0        // diagnostic builds only (TIMING what-ifs, results are wrong): bit 0 = the forward kernel's main loop issues no MFMAs, bit 1 = its
-#endif                      // epilogue stores nothing, bit 2 = its activation operand is read through an empty descriptor (every load returns zero, no traffic)
-#ifndef SSV_EXP_STAGGER
-#define SSV_EXP_STAGGER 0   // diagnostic builds only: see conv_fwd_k
-#endif
-#ifndef SSV_EXP_STAGGER_N
-#define SSV_EXP_STAGGER_N 3
-#endif
-#ifndef SSV_EXP_WGPRIO
-#define SSV_EXP_WGPRIO 0    // diagnostic builds only: 1 = every workgroup of the forward kernel takes a STATIC issue priority from its arrival order on its CU
-#endif                      // (consecutive arrivals get 0, 1, 2 -> s_setprio 0, 1, 3): does asymmetry between the residents break their lock-step?
-#ifndef SSV_EXP_PRIO
-#define SSV_EXP_PRIO 0      // diagnostic builds only: s_setprio level of a wave while it is in the MFMA part of a k-tile (0 = never raised, the shipped behaviour)
-#endif
-#ifndef SSV_CONV_WGPC
-#define SSV_CONV_WGPC 3     // resident workgroups per CU the forward / data-gradient kernels are compiled for
-#endif
-
 namespace {
-
-#if SSV_EXP_WGPRIO
-__device__ unsigned g_cu_arrivals[4096];
-__device__ __forceinline__ void wg_static_priority() {
-  __shared__ int s_prio;
-  if (threadIdx.x == 0) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);          // HW_REG_HW_ID: CU_ID [11:8], SH_ID [12], SE_ID [15:13]
-    const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);         // HW_REG_XCC_ID [3:0]
-    const unsigned idx = ((xcc & 15) << 8) | ((hw >> 8) & 0xff);
-    s_prio = (int)(atomicAdd(&g_cu_arrivals[idx & 4095], 1u) % 3u);
-  }
-  __syncthreads();
-  const int pr = s_prio;
-  if (pr == 2) __builtin_amdgcn_s_setprio(3);
-  else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);
-}
-#endif
 
 constexpr int GBK = 16;   // K-step of the generic (scalar gather) path and the granularity of wgrad row chunks
 
 // blocks b and b+8 share an XCD (and its L2): give each XCD a contiguous run of logical tiles so that tiles
 // sharing an operand panel hit the same L2.  Bijective for any grid size.  Speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-#ifdef SSV_NO_XCD_REMAP
-  return orig;
-#endif
   const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
@@ -95,7 +45,8 @@ struct ConvKP {
   int N, H, W, C, K, R, S, stride, pad, Ho, Wo;
   int M;              // fwd/wgrad: N*Ho*Wo
   int RSC;            // R*S*C
-  FastDiv dHoWo, dWo, dC, dS, dWp;   // dWp: W + 2 (the halo loader's records per staged row)
+  FastDiv dHoWo, dWo, dC, dS, dWp;   // dWp: unused (it served the removed halo loader).  Dropping it would move the offset of every kernel argument
+                                     // after it, so it stays until a change that alters the kernel arguments anyway
   float* aux_out;     // fused-activation variants only: forward also writes gelu(y) here; statistics variant: pmean
   float* aux_out2;    // statistics variant: pm2
   const float* aux_in;  //                                   dgrad multiplies by gelu'(aux_in) before the addend
@@ -130,16 +81,6 @@ __device__ __forceinline__ void group_span(int n0, int n1, int og, int ig, int b
   lo = glo * ig / bk * bk;
   hi = min(ctot, ((ghi + 1) * ig + bk - 1) / bk * bk);
 }
-
-// The halo loader (conv_fwd_k, C4 == 3): staged records (one pixel x 16 channels, 64 bytes at an 80-byte stride: ds_read_b128 of 16 consecutive pixels' fragments
-// then hit 16 distinct bank quads) a workgroup may hold PER STAGE - its 256 output pixels' rows plus one above and below, each with a padding record left and
-// right - and three records of zeros that out-of-image row taps are pointed at (one per column tap).  464 = 8 rows x 58 records (56 x 56 maps).  Two stages.
-constexpr int HALO_REC = 464;
-constexpr int HALO_RS = 20;                                   // record stride in floats
-constexpr int HALO_STAGE = (HALO_REC + 3) * HALO_RS;          // floats per stage
-constexpr int HALO_FLOATS = 2 * HALO_STAGE;
-// most records a 256-pixel tile of a W-wide map can need (the tile may start anywhere in a row)
-static inline int halo_records(int W) { return ((256 + W - 2) / W + 1 + 2) * (W + 2); }
 
 constexpr int XF_MAXC = 1024;   // input channels an XF forward kernel keeps (scale, shift) in LDS for
 
@@ -234,10 +175,6 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 }
 
-#ifdef SSV_STAMP
-__device__ unsigned long long g_stamps[8];
-#endif
-
 template <int TM, int TN> struct Frags { float a[TM][4], b[TN][4]; };
 
 // fragments of k-substep ks (8 k-values) of the staged tile: lane l takes k = 8*ks + 4*(l>>5) + t, t = 0..3
@@ -269,15 +206,6 @@ __device__ __forceinline__ void load_frags(Frags<TM, TN>& f, const float* __rest
 
 template <int TM, int TN>
 __device__ __forceinline__ void mma_frags(const Frags<TM, TN>& f, f32x16 (&acc)[TM][TN]) {
-#if SSV_WHATIF & 1
-  // what-if: the fragments are still read from LDS (kept alive by one add per fragment), no matrix instruction is issued
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[tm][tn][t] += f.a[tm][t] + f.b[tn][t];
-#else
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -285,7 +213,6 @@ __device__ __forceinline__ void mma_frags(const Frags<TM, TN>& f, f32x16 (&acc)[
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tm][t], f.b[tn][t], acc[tm][tn], 0, 0, 0);
-#endif
 }
 
 // compile-time interleave of one MFMA group with N memory instructions of kind `mask` (LLVM sched groups:
@@ -302,7 +229,7 @@ __device__ __forceinline__ void mma_frags(const Frags<TM, TN>& f, f32x16 (&acc)[
   } while (0)
 
 // K loop over staged tiles: ONE LDS stage, two barriers per tile (small LDS footprint -> 3 workgroups per CU hide each other's
-// barriers).  load_tile() issues the next tile's global loads into registers, store_tile(0) writes those registers to LDS.
+// barriers).  load_tile() issues the next tile's global loads into registers, store_tile() writes those registers to LDS.
 // xform_tile(): register-to-register transform of the prefetched tile (fused BatchNorm input / BatchNorm-backward operand), run right before
 // the tile is stored to LDS.  (Measured: issuing it under the last substep's MFMAs instead is SLOWER, 254.3 -> 256.0 ms per step - its
 // s_waitcnt for the prefetched loads then stalls that wave's MFMA stream one substep early.)
@@ -320,120 +247,47 @@ __device__ __forceinline__ void k_loop(int nkt, const float* As, const float* Bs
   constexpr int NM = 4 * TM * TN;            // MFMAs per substep
   load_tile();
   xform_tile();
-  store_tile(0);
+  store_tile();
   __syncthreads();
-  {
-#ifdef SSV_STAMP   // diagnostic build only (tools/): where does one k-tile spend its cycles?  Never in the shipped library.
-    unsigned long long t_ld = 0, t_mma = 0, t_b1 = 0, t_st = 0, t_b2 = 0;
-#define STAMP(var) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); var += now_ - last_; last_ = now_; } while (0)
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-#define STAMP(var) do {} while (0)
-#endif
-#ifdef SSV_STAMP
-    for (int kt = 0; kt < nkt; ++kt) {
-      const bool more = kt + 1 < nkt;
-      if (more) load_tile();                 // next tile's global loads fly under this tile's MFMAs
-      STAMP(t_ld);
-      mma_ktile<TM, TN, A_ROWK, B_ROWK, LDA, LDB, BK>(As, Bs, wr0, wc0, lane, acc);
-      STAMP(t_mma);
-      __syncthreads();
-      STAMP(t_b1);
-      if (more) { xform_tile(); store_tile(0); STAMP(t_st); __syncthreads(); STAMP(t_b2); }
-    }
-#else
-    // Branch-free body (one scheduling region per tile): the next tile's NLD buffer loads are issued one per MFMA of
-    // the first substep instead of in front of the MFMAs (a VMEM wave-instruction holds the issue port ~65 cycles).
-    // The loads issued during the last tile fall outside the operands and are never stored (buffer loads cannot fault).
-    Frags<TM, TN> fr;
-    for (int kt = 0; kt < nkt; ++kt) {
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (SSV_EXP_PRIO > 0) __builtin_amdgcn_s_setprio(SSV_EXP_PRIO);
-      load_frags<TM, TN, A_ROWK, B_ROWK, LDA, LDB>(fr, As, Bs, wr0, wc0, lane, 0);
-      load_tile();
-      mma_frags<TM, TN>(fr, acc);
-      if (NLD > 0) {
-        __builtin_amdgcn_sched_group_barrier(0x100, A_ROWK && B_ROWK ? TM + TN : (A_ROWK ? TM + 4 * TN : 4 * (TM + TN)), 0);
-        SSV_INTERLEAVE(NM, NLD, 0x20);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 1; ks < NS; ++ks) {
-        load_frags<TM, TN, A_ROWK, B_ROWK, LDA, LDB>(fr, As, Bs, wr0, wc0, lane, ks);
-        mma_frags<TM, TN>(fr, acc);
-      }
-      if constexpr (SSV_EXP_PRIO > 0) __builtin_amdgcn_s_setprio(0);
-      if constexpr (FLUSH > 0) {
-        if ((kt + 1) % FLUSH == 0) {               // uniform
-#pragma unroll
-          for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-              hi[tm][tn] += acc[tm][tn];
-#pragma unroll
-              for (int j = 0; j < 16; ++j) acc[tm][tn][j] = 0.f;
-            }
-        }
-      }
-      __syncthreads();
-      if (kt + 1 < nkt) { xform_tile(); store_tile(0); __syncthreads(); }
-    }
-    if constexpr (FLUSH > 0) {
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = hi[tm][tn] + acc[tm][tn];
-    }
-#endif
-#ifdef SSV_STAMP
-    if (threadIdx.x == 0) {
-      atomicAdd(&g_stamps[0], t_ld); atomicAdd(&g_stamps[1], t_mma); atomicAdd(&g_stamps[2], t_b1);
-      atomicAdd(&g_stamps[3], t_st); atomicAdd(&g_stamps[4], t_b2); atomicAdd(&g_stamps[5], (unsigned long long)nkt);
-    }
-#endif
-#undef STAMP
-  }
-}
-
-// Two LDS stages, ONE barrier per k-tile (round 4 experiment S2, plain GEMM-shaped launches with long k-loops only): tile kt is multiplied out of stage
-// kt & 1 while tile kt + 1 goes registers -> the other stage (its readers passed the last barrier) and tile kt + 2 global -> registers; the ds_writes are
-// interleaved one per MFMA of the first substep, the buffer loads one per MFMA of the second.  2 x 36.9 KB of LDS: 2 workgroups per CU.
-template <int TM, int TN, int LDT, int BK, int NLD, int STAGE_FLOATS, class LoadTile, class StoreTile>
-__device__ __forceinline__ void k_loop2(int nkt, const float* As, const float* Bs, int wr0, int wc0, int lane,
-                                        f32x16 (&acc)[TM][TN], LoadTile&& load_tile, StoreTile&& store_tile) {
-  if (nkt <= 0) return;
-  constexpr int NS = BK / 8;
-  constexpr int NM = 4 * TM * TN;
-  static_assert(NS >= 2, "two substeps carry the staging traffic");
-  load_tile();
-  store_tile(0);
-  load_tile();
-  __syncthreads();
+  // Branch-free body (one scheduling region per tile): the next tile's NLD buffer loads are issued one per MFMA of
+  // the first substep instead of in front of the MFMAs (a VMEM wave-instruction holds the issue port ~65 cycles).
+  // The loads issued during the last tile fall outside the operands and are never stored (buffer loads cannot fault).
   Frags<TM, TN> fr;
   for (int kt = 0; kt < nkt; ++kt) {
-    const float* a = As + (kt & 1) * STAGE_FLOATS;
-    const float* b = Bs + (kt & 1) * STAGE_FLOATS;
     __builtin_amdgcn_sched_barrier(0);
-    load_frags<TM, TN, true, true, LDT, LDT>(fr, a, b, wr0, wc0, lane, 0);
-    store_tile((kt + 1) & 1);                 // registers of tile kt + 1 (zeros past the last tile: never read)
+    load_frags<TM, TN, A_ROWK, B_ROWK, LDA, LDB>(fr, As, Bs, wr0, wc0, lane, 0);
+    load_tile();
     mma_frags<TM, TN>(fr, acc);
-    __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-    SSV_INTERLEAVE(NM, NLD, 0x200);
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags<TM, TN, true, true, LDT, LDT>(fr, a, b, wr0, wc0, lane, 1);
-    load_tile();                              // tile kt + 2 -> registers
-    mma_frags<TM, TN>(fr, acc);
-    __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-    SSV_INTERLEAVE(NM, NLD, 0x20);
+    if (NLD > 0) {
+      __builtin_amdgcn_sched_group_barrier(0x100, A_ROWK && B_ROWK ? TM + TN : (A_ROWK ? TM + 4 * TN : 4 * (TM + TN)), 0);
+      SSV_INTERLEAVE(NM, NLD, 0x20);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int ks = 2; ks < NS; ++ks) {
-      load_frags<TM, TN, true, true, LDT, LDT>(fr, a, b, wr0, wc0, lane, ks);
+    for (int ks = 1; ks < NS; ++ks) {
+      load_frags<TM, TN, A_ROWK, B_ROWK, LDA, LDB>(fr, As, Bs, wr0, wc0, lane, ks);
       mma_frags<TM, TN>(fr, acc);
     }
+    if constexpr (FLUSH > 0) {
+      if ((kt + 1) % FLUSH == 0) {               // uniform
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) {
+            hi[tm][tn] += acc[tm][tn];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[tm][tn][j] = 0.f;
+          }
+      }
+    }
     __syncthreads();
+    if (kt + 1 < nkt) { xform_tile(); store_tile(); __syncthreads(); }
+  }
+  if constexpr (FLUSH > 0) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = hi[tm][tn] + acc[tm][tn];
   }
 }
 
@@ -466,7 +320,7 @@ __device__ __forceinline__ void k_loop_split(int nkt, const unsigned char* As, i
   }
   load_tile();
   xform_tile();
-  store_tile(0);
+  store_tile();
   __syncthreads();
   for (int kt = 0; kt < nkt; ++kt) {
     load_tile();                               // past the last tile: out-of-range offsets read zeros (or in-buffer rows never stored)
@@ -508,7 +362,7 @@ __device__ __forceinline__ void k_loop_split(int nkt, const unsigned char* As, i
       }
     }
     __syncthreads();
-    if (kt + 1 < nkt) { xform_tile(); store_tile(0); __syncthreads(); }
+    if (kt + 1 < nkt) { xform_tile(); store_tile(); __syncthreads(); }
   }
 #pragma unroll
   for (int i = 0; i < TM16; ++i)
@@ -551,9 +405,6 @@ __device__ __forceinline__ void k_loop_split(int nkt, const unsigned char* As, i
 //      5 = multiply by the stored factor `gate` (= gelu'(h) written by 4) before the addend.
 __device__ __forceinline__ void bstore4(rsrc_t rs, int voff_bytes, f32x4 v) {
   typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
-#if SSV_WHATIF & 2
-  if (v[0] == 1.2345e38f)      // what-if: (practically) never true - the value stays live, no store reaches memory
-#endif
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), rs, voff_bytes, 0, 0);
 }
 
@@ -772,7 +623,7 @@ __device__ __forceinline__ void epilogue_vec(const Acc& acc, float* __restrict__
 // (a materialised tensor, or the raw projection-shortcut output with its own BatchNorm affine).  The tensor itself is still needed (next
 // residual add, weight gradient, backward mask), so the workgroups of column tile 0 also store it and its ReLU byte mask: the stand-alone
 // element-wise pass (2 reads + 1 write at the HBM roofline, overlapped with nothing) becomes one extra read and one write inside a convolution.
-template <int BM, int BN, int WGM, int WGN, int BK, bool VEC, int EPI = 0, bool STATS = false, int C4 = 0, bool XF = false, int GATE = 0, int OPM = 0, bool ADDS2 = false, bool S2 = false, int SP = 0>
+template <int BM, int BN, int WGM, int WGN, int BK, bool VEC, int EPI = 0, bool STATS = false, int C4 = 0, bool XF = false, int GATE = 0, int OPM = 0, bool ADDS2 = false, int SP = 0>
 // Resident workgroups per CU the variant is compiled for: 3 (they hide each other's barriers, loads and epilogues) wherever the registers allow.
 // The formed-on-load operands carry a second staged stream (ra2) and their per-channel coefficients: 188 - 236 VGPRs, i.e. 2 per CU - except
 // the BatchNorm-backward operand on the 128 x 128 tile, which fits 168 with five spilled dwords in the epilogue (r03 x1: 4 - 5 % faster on the
@@ -781,7 +632,8 @@ template <int BM, int BN, int WGM, int WGN, int BK, bool VEC, int EPI = 0, bool 
 // staged (after its formed-on-load transform), the weights arrive pre-split (p.w_planes), the main loop is k_loop_split and the accumulators are 16 x 16 tiles; every
 // epilogue is the fp32 variant's.  LDS: 192 bytes per staged row = 48 KB on the 128 x 128 tile (the fp32 image: 36.9 KB); narrow outputs (K < 128) take a 128 x 64
 // tile (36 KB, half the accumulators) where the fp32 variants take 256 x 64.
-__global__ void __launch_bounds__(256, SP ? ((OPM != 0 || GATE == 3 || (SP == 2 && BN == 128)) ? 2 : 3) : ((OPM == 2 || GATE == 3 || S2 || C4 == 3) ? 2 : (OPM == 1 ? ((BM == 128 && BN == 128) ? 3 : 2) : SSV_CONV_WGPC))) SSV_CONV_ATTR
+__global__ void __launch_bounds__(256, (SP ? (OPM != 0 || GATE == 3 || (SP == 2 && BN == 128))
+                                          : (OPM == 2 || GATE == 3 || (OPM == 1 && !(BM == 128 && BN == 128)))) ? 2 : 3)
 conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
            const float* addend, float* y) {
   constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
@@ -791,14 +643,11 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
   constexpr bool DYF = OPM == 1, SUM = OPM == 2;
   static_assert(OPM == 0 || (VEC && C4 == 0 && !XF), "the formed-on-load operands are the float4 path");
   constexpr int EP_FLOATS = 4 * 32 * (TN * 32 + 4);     // the vectorised epilogue's staging area (one 32-row slab per wave)
-  static_assert(!S2 || (VEC && C4 == 0 && !XF && OPM == 0), "the two-stage loop serves the plain float4 path");
-  static_assert(C4 != 3 || (VEC && BM == 256 && BK == 32 && TM == 2 && !XF && OPM == 0 && !S2 && EP_FLOATS <= HALO_FLOATS), "the halo loader serves the 256-row tile of the plain float4 path");
-  static_assert(!SP || (VEC && C4 == 0 && !S2 && BK == 32), "the bf16-piece variants are the float4 path with K-step 32");
+  static_assert(!SP || (VEC && C4 == 0 && BK == 32), "the bf16-piece variants are the float4 path with K-step 32");
   constexpr int SP_FLOATS = (BM + BN) * 48;             // three planes of 64-byte rows per operand
   constexpr int SMEM = SP ? (SP_FLOATS > EP_FLOATS ? SP_FLOATS : EP_FLOATS)
-                          : (C4 == 3 ? HALO_FLOATS : (S2 ? 2 * STAGE : ((VEC && (EPI || STATS || GATE != 0 || OPM != 0) && EP_FLOATS > STAGE) ? EP_FLOATS : STAGE)));
-  static_assert(!S2 || 2 * STAGE >= EP_FLOATS, "epilogue staging must fit the two stages");
-  __shared__ __attribute__((aligned(16))) float smem[SMEM + SSV_EXP_LDS_PAD];
+                          : ((VEC && (EPI || STATS || GATE != 0 || OPM != 0) && EP_FLOATS > STAGE) ? EP_FLOATS : STAGE);
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
   __shared__ __attribute__((aligned(16))) float xfs[(XF && !SP) ? 2 * XF_MAXC : 4];    // [scale | shift] of the fused input BatchNorm (SP: read per k-tile, the LDS is the planes')
   float* As = smem;
   float* Bs = smem + BM * LDT;
@@ -819,17 +668,6 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
 #pragma unroll
       for (int j = 0; j < 2 * TN; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   } else zero_acc<SP ? 1 : TM, SP ? 1 : TN>(acc);
-#if SSV_EXP_WGPRIO
-  wg_static_priority();
-#endif
-#if SSV_EXP_STAGGER
-  // diagnostic builds only: the workgroups of the first resident round start SSV_EXP_STAGGER x 3.4 us apart (by their position in that round), so that the
-  // workgroups sharing a CU are not in the same phase (prologue / main loop / epilogue) for the rest of the launch
-  if (blockIdx.x < 256u * SSV_EXP_STAGGER_N) {
-    const int ph = (int)(blockIdx.x >> 8) % SSV_EXP_STAGGER_N;
-    for (int i = 0; i < ph * SSV_EXP_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
 
   if constexpr (VEC && C4 == 2) {
     // ---- the image stem on the UNPADDED 3-channel input: for one filter row r the S taps x 3 channels of an output pixel are 3 S CONTIGUOUS
@@ -840,7 +678,7 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
     static_assert(BK == 24 && BM == 256, "one staged output row per thread, six float4 per row");
     constexpr int CHN = BK / 4;
     constexpr int BF = (BN * CHN + 255) / 256;                     // weight float4s per thread
-    const rsrc_t rx = make_rsrc(x, (SSV_WHATIF & 4) ? 0u : (unsigned)p.N * p.H * p.W * 12u);
+    const rsrc_t rx = make_rsrc(x, (unsigned)p.N * p.H * p.W * 12u);
     const rsrc_t rw = make_rsrc(w, (unsigned)p.K * p.R * BK * 4u);
     int hi0, rowbase;
     unsigned wmask = 0;                                            // bit px: tap column px of this output pixel lies inside the image row
@@ -892,7 +730,7 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
 #pragma unroll
         for (int e = 0; e < 4; ++e) ra[j][e] = ((wmask >> ((4 * j + e) / 3)) & 1u) ? ra[j][e] : 0.f;
     };
-    auto store_tile = [&](int buf) {
+    auto store_tile = [&]() {
 #pragma unroll
       for (int j = 0; j < CHN; ++j) *reinterpret_cast<f32x4*>(&As[tid * LDT + 4 * j]) = ra[j];
 #pragma unroll
@@ -947,127 +785,13 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
       for (int i = 0; i < BP; ++i) rb[i] = bload4(rw, (tv && boff[i] != OOB_OFF) ? boff[i] + toff_w : OOB_OFF, 0);
       lt += CH;
     };
-    auto store_tile = [&](int buf) {
+    auto store_tile = [&]() {
 #pragma unroll
       for (int i = 0; i < AP; ++i) *reinterpret_cast<f32x4*>(&As[(rsub + RPP * i) * LDT + tl * 4]) = ra[i];
 #pragma unroll
       for (int i = 0; i < BP; ++i) *reinterpret_cast<f32x4*>(&Bs[(rsub + RPP * i) * LDT + tl * 4]) = rb[i];
     };
     k_loop<TM, TN, true, true, LDT, LDT, BK, AP + BP>((ntap + CH - 1) / CH, As, Bs, wr0, wc0, lane, acc, load_tile, store_tile);
-  } else if constexpr (VEC && C4 == 3) {
-    // ---- 3x3 / stride 1 / padding 1 with C % 32 == 0 on the 256 x 64 tile (networks/resnet.py:7-10,56-58: conv2 of the 64-channel units; its data gradient is the
-    //      same product with the rotated filter): HALO staging.  The generic loader below stages every pixel NINE times per channel chunk (once per tap: 18 k-tiles
-    //      of predicated loads, LDS writes and two barriers each for 64 channels); here the pixels the tile's 256 outputs can see - their image rows plus one above
-    //      and below, a zero record left and right of each row - go to LDS ONCE per 16-channel chunk as 64-byte records, and the nine taps are nine record offsets
-    //      of the same staged data.  Two LDS stages: the next chunk's global loads are issued before the current chunk's 288 MFMAs per wave and written to the
-    //      other stage after them - ONE barrier per chunk, none inside it, and the loads of all resident workgroups spread over the matrix phase instead of
-    //      arriving as one burst (one stage of 32 channels, measured: the chip's workgroups run in lockstep, so their staging bursts and their MFMA phases
-    //      alternated instead of overlapping - 107 TFLOP/s, the generic loader's figure).  A lane's A fragment is the 8 consecutive channels 8 * half .. of its
-    //      pixel's record (two ds_read_b128 at immediate offsets of one address register per row tap), its B fragment the same 8 channels of its output column's
-    //      filter tap, read straight from the (L2-resident) filter into registers - the weights never touch LDS; both are fetched one tap (32 MFMAs) ahead,
-    //      one memory instruction per MFMA.  Rows of a neighbouring image that sit above / below an image's first / last row are real data in LDS (their own
-    //      pixels need them): a lane whose pixel's tap row falls outside its image reads the records of zeros instead. ----
-    const int WP = p.W + 2;
-    const rsrc_t rx = make_rsrc(x, (SSV_WHATIF & 4) ? 0u : (unsigned)p.N * p.H * p.W * p.C * 4u);
-    const rsrc_t rw = make_rsrc(w, (unsigned)p.K * p.RSC * 4u);
-    const int l31 = lane & 31, half = lane >> 5;
-    const int g0 = (int)fdiv((uint32_t)m0, p.dWo);                          // running row index n * H + ho of the tile's first pixel (uniform)
-    const int nrec = ((int)fdiv((uint32_t)(min(m0 + BM, p.M) - 1), p.dWo) - g0 + 3) * WP;      // staged records (<= HALO_REC: checked by the launcher)
-    // per lane and row tap dr: LDS float offset (within a stage) of its pixels' fragment in the centre column, or of the middle zero record where the row is
-    // outside the image; the stage, the column tap and the 16-byte piece are immediate offsets of the ds_read
-    int abase[TM][3];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const uint32_t m = (uint32_t)min(m0 + wr0 + tm * 32 + l31, p.M - 1);  // rows past M repeat the last pixel: never stored nor counted
-      const uint32_t g = fdiv(m, p.dWo), n = fdiv(m, p.dHoWo);
-      const int hrow = (int)(g - n * (uint32_t)p.H);
-      const int P0 = ((int)g - g0 + 1) * WP + (int)(m - g * (uint32_t)p.W) + 1;
-#pragma unroll
-      for (int dr = -1; dr <= 1; ++dr)
-        abase[tm][dr + 1] = (((unsigned)(hrow + dr) < (unsigned)p.H) ? P0 + dr * WP : HALO_REC + 1) * HALO_RS + 8 * half;
-    }
-    int wofs[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      const int ko = n0 + wc0 + tn * 32 + l31;
-      wofs[tn] = ko < p.K ? (ko * p.RSC + 8 * half) * 4 : OOB_OFF;
-    }
-    constexpr int NLD = (HALO_REC * 4 + 255) / 256;
-    int soff[NLD];                                                          // byte offset of this thread's staged float4s in x (channel chunk 0)
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int e = tid + 256 * i, rec = e >> 2, slot = e & 3;
-      const int j = (int)fdiv((uint32_t)rec, p.dWp), col = rec - j * WP, g = g0 - 1 + j;
-      const bool ok = (rec < nrec) & (col >= 1) & (col <= p.W) & ((unsigned)g < (unsigned)(p.N * p.H));
-      soff[i] = ok ? ((g * p.W + col - 1) * p.C + slot * 4) * 4 : OOB_OFF;
-    }
-    f32x4 st[NLD];
-    auto issue_stage = [&](int c0) {
-#pragma unroll
-      for (int i = 0; i < NLD; ++i) st[i] = bload4(rx, soff[i], c0 * 4);
-    };
-    auto write_stage = [&](int stage) {
-#pragma unroll
-      for (int i = 0; i < NLD; ++i) {
-        const int e = tid + 256 * i, rec = e >> 2, slot = e & 3;
-        if (rec < nrec) *reinterpret_cast<f32x4*>(&smem[stage * HALO_STAGE + rec * HALO_RS + slot * 4]) = st[i];
-      }
-    };
-    f32x4 bq[2][TN][2], aq[2][TM][2];
-    auto load_b = [&](f32x4 (&b)[TN][2], int tap, int c0) {
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) b[tn][q] = bload4(rw, ((SSV_WHATIF & 8) ? 0 : wofs[tn]) + q * 16, (tap * p.C + c0) * 4);      // (OOB_OFF + 16 is still out of range)
-    };
-    auto load_a = [&](f32x4 (&a)[TM][2], int tap, int stage) {
-      const int dr = tap / 3, dc = tap % 3 - 1;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) a[tm][q] = *reinterpret_cast<const f32x4*>(&smem[abase[tm][dr] + stage * HALO_STAGE + dc * HALO_RS + 4 * q]);
-    };
-    issue_stage(0);
-    load_b(bq[0], 0, 0);
-    for (int i = tid; i < 2 * 3 * HALO_RS; i += 256) smem[(i / (3 * HALO_RS)) * HALO_STAGE + HALO_REC * HALO_RS + i % (3 * HALO_RS)] = 0.f;
-    write_stage(0);
-    __syncthreads();
-    const int nch = p.C / 16;                                               // even: C % 32 == 0
-#pragma unroll 1
-    for (int ch2 = 0; ch2 < nch; ch2 += 2) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {                                         // chunk ch2 + u lives in stage u
-        const int c0 = (ch2 + u) * 16;
-        const bool more = ch2 + u + 1 < nch;
-        if (more) issue_stage(c0 + 16);
-        load_a(aq[(u * 9) & 1], 0, u);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-          constexpr int NMF = 8 * TM * TN;                                  // MFMAs per tap
-          const int cur = (u * 9 + tap) & 1;
-          __builtin_amdgcn_sched_barrier(0);
-          if (tap < 8) { load_b(bq[cur ^ 1], tap + 1, c0); load_a(aq[cur ^ 1], tap + 1, u); }
-          else if (more) load_b(bq[cur ^ 1], 0, c0 + 16);                   // the next chunk's first filter tap (its A fragments wait for the stage)
-#pragma unroll
-          for (int ks = 0; ks < ((SSV_WHATIF & 1) ? 2 : 8); ++ks)          // (timing what-if: a quarter of the MFMAs, every fragment load still consumed)
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-              for (int tn = 0; tn < TN; ++tn)
-                acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[cur][tm][(SSV_WHATIF & 1) ? ks : (ks >> 2)][ks & 3], bq[cur][tn][(SSV_WHATIF & 1) ? ks : (ks >> 2)][ks & 3], acc[tm][tn], 0, 0, 0);
-          if (tap < 8 && !(SSV_WHATIF & 1)) {
-#pragma unroll
-            for (int i_ = 0; i_ < 2 * TN; ++i_) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 1, 0); }
-#pragma unroll
-            for (int i_ = 0; i_ < 2 * TM; ++i_) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x8, NMF - 2 * TN - 2 * TM, 0);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (more) write_stage(u ^ 1);                                       // its last readers passed the previous chunk's barrier
-        __syncthreads();
-      }
-    }
   } else if constexpr (VEC) {
     // ---- C % BK == 0: every k-tile lies inside one filter tap; float4 staging, BK/4 lanes per row ----
     constexpr int CH = BK / 4, RPP = 256 / CH;
@@ -1075,7 +799,7 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
     const int chunk = (tid % CH) * 4, rsub = tid / CH;
     // Loader state per staged row: byte offset of (n, hi0, wi0, chunk) in x, top-left input coordinate.  Per tile the
     // tap adds ONE uniform offset; invalid rows / taps get the out-of-range offset and come back as zeros.
-    const rsrc_t rx = make_rsrc(x, (SSV_WHATIF & 4) ? 0u : (unsigned)p.N * p.H * p.W * p.C * 4u);
+    const rsrc_t rx = make_rsrc(x, (unsigned)p.N * p.H * p.W * p.C * 4u);
     const rsrc_t rw = make_rsrc(w, (unsigned)p.K * p.RSC * 4u);
     int hi0[AP], wi0[AP], aoff[AP];
 #pragma unroll
@@ -1231,7 +955,7 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
     constexpr int A_PLANE = BM * splitbf::ROWB, B_PLANE = BN * splitbf::ROWB;
     unsigned char* const Asb = reinterpret_cast<unsigned char*>(smem);
     unsigned char* const Bsb = Asb + 3 * A_PLANE;
-    auto store_tile = [&](int buf) {
+    auto store_tile = [&]() {
       if constexpr (SP) {
 #pragma unroll
         for (int i = 0; i < AP; ++i) splitbf::rowk_store(Asb, A_PLANE, rsub + RPP * i, tid % CH, ra[i]);
@@ -1242,14 +966,12 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
             if (BN * 4 % 256 == 0 || tid + 256 * i < BN * 4) *reinterpret_cast<u32x4*>(Bsb + q * B_PLANE + bldsp[i]) = rbp[q][i];
         return;
       }
-      const int so = S2 ? buf * STAGE : 0;
 #pragma unroll
-      for (int i = 0; i < AP; ++i) *reinterpret_cast<f32x4*>(&As[so + (rsub + RPP * i) * LDT + chunk]) = ra[i];
+      for (int i = 0; i < AP; ++i) *reinterpret_cast<f32x4*>(&As[(rsub + RPP * i) * LDT + chunk]) = ra[i];
 #pragma unroll
-      for (int i = 0; i < BP; ++i) *reinterpret_cast<f32x4*>(&Bs[so + (rsub + RPP * i) * LDT + chunk]) = rb[i];
+      for (int i = 0; i < BP; ++i) *reinterpret_cast<f32x4*>(&Bs[(rsub + RPP * i) * LDT + chunk]) = rb[i];
     };
     if constexpr (SP) k_loop_split<2 * TM, 2 * TN, false, false, 128, 128, 0, 1, SP == 2>(ktiles, Asb, A_PLANE, Bsb, B_PLANE, wr0, wc0, lane, acc16, load_tile, store_tile, xform_tile);
-    else if constexpr (S2) k_loop2<TM, TN, LDT, BK, AP + BP, STAGE>(ktiles, As, Bs, wr0, wc0, lane, acc, load_tile, store_tile);
     else k_loop<TM, TN, true, true, LDT, LDT, BK, AP + BP + (OPM ? AP + 4 : 0)>(ktiles, As, Bs, wr0, wc0, lane, acc, load_tile, store_tile, xform_tile);
   } else {
     // ---- generic gather (any C; used by the 3-channel stem): scalar staging, k -> (r,s,c) per element ----
@@ -1387,13 +1109,13 @@ conv_fwd_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ w, c
 // SP (SSV_ARITH_BF16X3; the 128 x 128 tile with K-step 32): dY rows are split while they are staged (ROWK planes), the weights arrive pre-split (p.w_planes) and keep their
 // k-major image ([32 output channels][input channels] per plane), read by transposed reads.
 template <int BM, int BN, int WGM, int WGN, int BK, bool EPI = false, int GATE = 0, bool SP = false>
-__global__ void __launch_bounds__(256, SP ? 2 : SSV_CONV_WGPC) SSV_CONV_ATTR      // 3 workgroups per CU: they hide each other's barriers, loads and epilogues
+__global__ void __launch_bounds__(256, SP ? 2 : 3)      // 3 workgroups per CU: they hide each other's barriers, loads and epilogues
 conv_dgrad_k(ConvKP p, const float* __restrict__ dy, const float* __restrict__ w, const float* addend, float* dx) {
   constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
   constexpr int LDT = BK + 4;
   static_assert(!SP || (BK == 32 && BN == 128), "the bf16-piece data gradient: K-step 32, 128 input channels per tile");
   constexpr int A_FLOATS = BM * LDT, B_FLOATS = BK * BN, STAGE = SP ? 48 * (BM + BN) : A_FLOATS + B_FLOATS;
-  __shared__ __attribute__((aligned(16))) float smem[STAGE + SSV_EXP_LDS_PAD];
+  __shared__ __attribute__((aligned(16))) float smem[STAGE];
   __shared__ unsigned rowpix[BM];
   __shared__ int taps[64 * 3];      // (dho, dwo, tapoff) per valid tap
   __shared__ int ntaps_s;
@@ -1537,7 +1259,7 @@ conv_dgrad_k(ConvKP p, const float* __restrict__ dy, const float* __restrict__ w
   constexpr int A_PLANE = BM * splitbf::ROWB, B_PLANE = 32 * BN * 2;
   unsigned char* const Asb = reinterpret_cast<unsigned char*>(smem);
   unsigned char* const Bsb = Asb + 3 * A_PLANE;
-  auto store_tile = [&](int buf) {
+  auto store_tile = [&]() {
     if constexpr (SP) {
 #pragma unroll
       for (int i = 0; i < AP; ++i) splitbf::rowk_store(Asb, A_PLANE, rsub + RPP * i, tid % CH, ra[i]);
@@ -1830,7 +1552,7 @@ conv_wgrad_k(ConvKP p, const float* __restrict__ x, const float* __restrict__ dy
   constexpr int A_PLANE = 32 * BM * 2, B_PLANE = 32 * BN * 2;            // SP: bytes of one plane of the dY / X image
   unsigned char* const Asb = reinterpret_cast<unsigned char*>(smem);
   unsigned char* const Bsb = Asb + 3 * A_PLANE;
-  auto store_tile = [&](int buf) {
+  auto store_tile = [&]() {
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
       if constexpr (SP) splitbf::krow_store<BM * 2>(Asb, A_PLANE, arow + ARP * i, acol, ra[i]);
@@ -1964,9 +1686,6 @@ WgradPlan plan_wgrad(const ssv_conv_desc* d, int groups = 0) {
   const bool bd = groups > 1 && d->C % 64 == 0;     // block-diagonal bank: 64 x 64 tiles, of which only those a group touches do any work
   w.bm = (d->K >= 128 && !bd) ? 128 : 64;
   w.bn = (RSC <= 64 || bd) ? 64 : 128;      // 1x1 convs on 64 channels: a 128-wide tile would be half empty
-#ifdef SSV_EXP_WGRAD_BN64                   // diagnostic builds only (round 6): the bf16x3 weight gradient on 128 x 64 tiles (half the accumulator registers: 3-4 workgroups per CU)
-  if (d->arithmetic == SSV_ARITH_BF16X3 && w.bm == 128) w.bn = 64;
-#endif
   w.it = cdiv(d->K, w.bm);
   w.jt = cdiv(RSC, w.bn);
   int tiles = w.it * w.jt;
@@ -2037,32 +1756,19 @@ int launch_fwd(const ssv_conv_desc* d, const float* x, const float* w, const flo
   // (1x1 layers with few k-tiles - 64 -> 256 at 56x56 runs at 2.7 TB/s and 69 TFLOP/s, the SUM of its MFMA and HBM times - were tried on a 128 x 64 tile
   //  at 4 / 5 workgroups per CU, on a 64 x 256 tile writing whole 1 KB rows and as a persistent kernel that loads its next tile under the epilogue: no change, r03 x3)
   const unsigned grid = (unsigned)(wide ? cdiv(p.M, 128) * cdiv(d->K, 128) : (sp ? cdiv(p.M, 128) : cdiv(p.M, 256)) * cdiv(d->K, 64));
-  // 3x3 / stride 1 / padding 1 on the 256 x 64 tile: the halo loader (conv_fwd_k, C4 == 3) when the tile's rows fit its LDS records.  DIAGNOSTIC BUILDS ONLY
-  // (-DSSV_EXP_HALO, round 4): three different main loops for this layer - the generic one, one halo stage of 32 channels, two halo stages of 16 - all land on
-  // 104-109 TFLOP/s, because the kernel already keeps the matrix pipe 0.80-0.82 busy and the chip clocks it at 2.0-2.1 GHz under that load
-  // (profiles/r04_probe_halo_loader.txt); the shipped library keeps the one generic loader.
-#ifdef SSV_EXP_HALO
-  const bool halo = !wide && groups <= 1 && !xf && add_H2 == 0 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && d->C % 32 == 0 && d->K % 4 == 0 &&
-                    d->Ho == d->H && d->Wo == d->W && halo_records(d->W) <= HALO_REC;
-#endif
+  // (3x3 / stride 1 / padding 1 on the 256 x 64 tile, round 4: a halo loader that stages every pixel once per channel chunk instead of once per tap, with one or
+  //  two LDS stages, lands on 104-109 TFLOP/s like the generic loader - the kernel already keeps the matrix pipe 0.80-0.82 busy and the chip clocks it at
+  //  2.0-2.1 GHz under that load; profiles/r04_probe_halo_loader.txt)
   if (gate) {                                                  // C % 32 == 0 checked by the caller
     p.gate = *gate;
-#ifdef SSV_EXP_HALO
-    if (halo) {
-#define FWDGH(G_) hipLaunchKernelGGL((conv_fwd_k<256, 64, 4, 1, 32, true, 0, false, 3, false, G_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
-      if (gate->x2) FWDGH(3); else if (gate->mask) FWDGH(2); else FWDGH(1);
-#undef FWDGH
-      return SSV_OK;
-    }
-#endif
 #define FWDG_(BM_, BN_, WM_, WN_, G_, SP_) \
-  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, false, false, false, G_, 0, false, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
+  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, false, false, false, G_, 0, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
 #define FWDG(BM_, BN_, WM_, WN_, G_) FWDG_(BM_, BN_, WM_, WN_, G_, 0)
 #define FWDG_TILE(G_) do { if (sp == 2) { if (wide) FWDG_(128, 128, 2, 2, G_, 2); else FWDG_(128, 64, 2, 2, G_, 2); } \
                            else if (sp) { if (wide) FWDG_(128, 128, 2, 2, G_, 1); else FWDG_(128, 64, 2, 2, G_, 1); } \
                            else    { if (wide) FWDG(128, 128, 2, 2, G_); else FWDG(256, 64, 4, 1, G_); } } while (0)
     if (add_H2 > 0) {                                          // compact stride-2 addend: wide tile, byte-mask gates (checked by the caller)
-#define FWDGS_(G_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false, G_, 0, true, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
+#define FWDGS_(G_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false, G_, 0, true, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
 #define FWDGS(G_) do { if (sp == 2) FWDGS_(G_, 2); else if (sp) FWDGS_(G_, 1); else FWDGS_(G_, 0); } while (0)
       if (gate->x2) FWDGS(3); else FWDGS(2);
 #undef FWDGS
@@ -2074,7 +1780,7 @@ int launch_fwd(const ssv_conv_desc* d, const float* x, const float* w, const flo
     return SSV_OK;
   }
 #define FWD_(BM_, BN_, WM_, WN_, BK_, ST_, C4_, XF_, SP_) \
-  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, BK_, true, false, ST_, C4_, XF_, 0, 0, false, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
+  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, BK_, true, false, ST_, C4_, XF_, 0, 0, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
 #define FWD(BM_, BN_, WM_, WN_, BK_, ST_, C4_, XF_) FWD_(BM_, BN_, WM_, WN_, BK_, ST_, C4_, XF_, 0)
 // the float4 path with K-step 32: either arithmetic
 #define FWD_TILE_A(ST_, XF_) do { \
@@ -2082,11 +1788,6 @@ int launch_fwd(const ssv_conv_desc* d, const float* x, const float* w, const flo
     else if (sp) { if (wide) FWD_(128, 128, 2, 2, 32, ST_, 0, XF_, 1); else FWD_(128, 64, 2, 2, 32, ST_, 0, XF_, 1); } \
     else    { if (wide) FWD_(128, 128, 2, 2, 32, ST_, 0, XF_, 0); else FWD_(256, 64, 4, 1, 32, ST_, 0, XF_, 0); } } while (0)
 #define FWD_TILE(BK_, ST_, C4_, XF_) do { if (wide) FWD(128, 128, 2, 2, BK_, ST_, C4_, XF_); else FWD(256, 64, 4, 1, BK_, ST_, C4_, XF_); } while (0)
-#ifdef SSV_EXP_HALO
-  if (halo) {
-    if (stats) FWD(256, 64, 4, 1, 32, true, 3, false); else FWD(256, 64, 4, 1, 32, false, 3, false);
-  } else
-#endif
   if (stats && d->C == 4) {                                    // the padded image stem with the statistics epilogue
     FWD_TILE(32, true, true, false);
   } else if (stats || xf) {                                    // C % 32 == 0 checked by the callers
@@ -2096,12 +1797,6 @@ int launch_fwd(const ssv_conv_desc* d, const float* x, const float* w, const flo
   } else if (d->C == 4) {                                      // image stems (3 channels padded to 4): tap-vector gather
     FWD_TILE(32, false, true, false);
   } else if (d->C % 32 == 0) {
-#ifdef SSV_EXP_S2      // diagnostic builds only: two-stage main loop for wide plain launches with at least SSV_EXP_S2 k-tiles
-    if (wide && groups <= 1 && p.RSC / 32 >= SSV_EXP_S2) {
-      hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 0, false, 0, false, 0, 0, false, true>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y);
-      return SSV_OK;
-    }
-#endif
     FWD_TILE_A(false, false);
   } else if (d->C % 16 == 0) {
     FWD_TILE(16, false, false, false);
@@ -2231,13 +1926,13 @@ int fwd_dyin_impl(const ssv_conv_desc* d, const float* g, const ssv_bn_dyin* dyi
   const unsigned grid = (unsigned)(wide ? cdiv(p.M, 128) * cdiv(d->K, 128) : (sp ? cdiv(p.M, 128) : cdiv(p.M, 256)) * cdiv(d->K, 64));
   const int gm = gate ? (gate->x2 ? 3 : (gate->mask ? 2 : 1)) : 0;
 #define FWDD_(BM_, BN_, WM_, WN_, G_, SP_) \
-  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, false, false, false, G_, 1, false, false, SP_>), dim3(grid), dim3(256), 0, s, p, g, w, (const float*)nullptr, addend, y)
+  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, false, false, false, G_, 1, false, SP_>), dim3(grid), dim3(256), 0, s, p, g, w, (const float*)nullptr, addend, y)
 #define FWDD(BM_, BN_, WM_, WN_, G_) FWDD_(BM_, BN_, WM_, WN_, G_, 0)
 #define FWDD_TILE(G_) do { if (sp == 2) { if (wide) FWDD_(128, 128, 2, 2, G_, 2); else FWDD_(128, 64, 2, 2, G_, 2); } \
                            else if (sp) { if (wide) FWDD_(128, 128, 2, 2, G_, 1); else FWDD_(128, 64, 2, 2, G_, 1); } \
                            else    { if (wide) FWDD(128, 128, 2, 2, G_); else FWDD(256, 64, 4, 1, G_); } } while (0)
   if (add_H2 > 0) {                                          // compact stride-2 addend: wide tile and byte-mask gate checked by the caller
-#define FWDDS_(G_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false, G_, 1, true, false, SP_>), dim3(grid), dim3(256), 0, s, p, g, w, (const float*)nullptr, addend, y)
+#define FWDDS_(G_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false, G_, 1, true, SP_>), dim3(grid), dim3(256), 0, s, p, g, w, (const float*)nullptr, addend, y)
 #define FWDDS(G_) do { if (sp == 2) FWDDS_(G_, 2); else if (sp) FWDDS_(G_, 1); else FWDDS_(G_, 0); } while (0)
     if (gm == 3) FWDDS(3); else FWDDS(2);
 #undef FWDDS
@@ -2287,7 +1982,7 @@ extern "C" int ssv_conv2d_fwd_sumin_stats(const ssv_conv_desc* d, const float* x
   const bool wide = d->K >= 128;
   const int sp = sp_fwd_mode(d);
   const unsigned grid = wide ? (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128)) : (unsigned)((sp ? cdiv(p.M, 128) : cdiv(p.M, 256)) * cdiv(d->K, 64));
-#define FWDS(BM_, BN_, WM_, WN_, SP_) hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, true, false, false, 0, 2, false, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, (const float*)nullptr, (const float*)nullptr, y)
+#define FWDS(BM_, BN_, WM_, WN_, SP_) hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, true, false, false, 0, 2, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, (const float*)nullptr, (const float*)nullptr, y)
   if (sp == 2) { if (wide) FWDS(128, 128, 2, 2, 2); else FWDS(128, 64, 2, 2, 2); }
   else if (sp) { if (wide) FWDS(128, 128, 2, 2, 1); else FWDS(128, 64, 2, 2, 1); }
   else    { if (wide) FWDS(128, 128, 2, 2, 0); else FWDS(256, 64, 4, 1, 0); }
@@ -2337,13 +2032,7 @@ extern "C" int ssv_linear_gelu_fwd(const ssv_conv_desc* d, const float* x, const
   p.aux_out = act;
   const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
   // K-step 32 only: its LDS stage is what the vectorised epilogue (the one that writes the second tensor) needs
-#ifdef SSV_EXP_S2
-  if (p.RSC / 32 >= SSV_EXP_S2) {
-    if (h) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 1, false, 0, false, 0, 0, false, true>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, h);
-    else   hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 3, false, 0, false, 0, 0, false, true>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, act);
-  } else
-#endif
-#define FWDE(E_, SP_, OUT_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, E_, false, 0, false, 0, 0, false, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, OUT_)
+#define FWDE(E_, SP_, OUT_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, E_, false, 0, false, 0, 0, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, OUT_)
   const int sp = sp_fwd_mode(d);
   if (sp == 2)  { if (h) FWDE(1, 2, h); else FWDE(3, 2, act); }
   else if (sp)  { if (h) FWDE(1, 1, h); else FWDE(3, 1, act); }
@@ -2386,13 +2075,8 @@ extern "C" int ssv_linear_fwd_gelugrad(const ssv_conv_desc* d, const float* dy, 
   ConvKP p = make_kp(d);
   p.aux_in = h;
   const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
-#ifdef SSV_EXP_S2
-  if (p.RSC / 32 >= SSV_EXP_S2)
-    hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, true>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else
-#endif
-  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, false, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, false, 1>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
+  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
+  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, 1>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
   else hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
   SSV_CHECK_LAUNCH("ssv_linear_fwd_gelugrad");
   return SSV_OK;
@@ -2410,8 +2094,8 @@ extern "C" int ssv_linear_gelu_fwd_dact(const ssv_conv_desc* d, const float* x, 
   ConvKP p = make_kp(d);
   p.aux_out = act;
   const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
-  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4, false, 0, false, 0, 0, false, false, 2>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
-  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4, false, 0, false, 0, 0, false, false, 1>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
+  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4, false, 0, false, 0, 0, false, 2>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
+  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4, false, 0, false, 0, 0, false, 1>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
   else hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
   SSV_CHECK_LAUNCH("ssv_linear_gelu_fwd_dact");
   return SSV_OK;
@@ -2429,8 +2113,8 @@ extern "C" int ssv_linear_fwd_mulgrad(const ssv_conv_desc* d, const float* dy, c
   ConvKP p = make_kp(d);
   p.aux_in = dact;
   const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
-  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5, false, 0, false, 0, 0, false, false, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5, false, 0, false, 0, 0, false, false, 1>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
+  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5, false, 0, false, 0, 0, false, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
+  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5, false, 0, false, 0, 0, false, 1>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
   else hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
   SSV_CHECK_LAUNCH("ssv_linear_fwd_mulgrad");
   return SSV_OK;
@@ -2677,9 +2361,6 @@ constexpr int SF_ROWS = 9, SF_ROWF = 728, SF_K = 64, SF_NT = 448, SF_MAXSTEPS = 
 constexpr int SF_NX = (SF_ROWS * (SF_ROWF / 4) + SF_NT - 1) / SF_NT;
 
 static inline int stem_fwd_rows_rpi(const ssv_conv_desc* d) {       // output rows per iteration, 0 = this launch runs on the row-taps kernel
-#ifdef SSV_NO_STEM_ROWS
-  return 0;
-#endif
   const int padl = (d->pad * 3 + 3) / 4 * 4, off = padl - d->pad * 3;
   if (!(d->C == 3 && d->K == SF_K && d->R <= 7 && d->S * 3 <= 24 && d->R * ((d->S * 3 + 1) / 2) <= SF_MAXSTEPS && d->W % 4 == 0 &&
         padl + d->W * 3 <= SF_ROWF && off + (d->Wo - 1) * d->stride * 3 + 24 <= SF_ROWF && (int64_t)d->N * d->H * d->W * 12 < (1ll << 31)))
@@ -2755,8 +2436,8 @@ stem_fwd_rows_k(ConvKP p, const float* __restrict__ x, const float* __restrict__
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j)       // (32 consecutive channels of a pixel per half-wave: 128-byte segments.  Timing what-if 2: no stores - 1.40 -> 1.27 ms at bs 512)
-          if (!(SSV_WHATIF & 2) || acc[tn][j] == 12345.f) y[(m0 + (j & 3) + 8 * (j >> 2) + 4 * half) * SF_K + 32 * tn + l31] = acc[tn][j];
+        for (int j = 0; j < 16; ++j)       // (32 consecutive channels of a pixel per half-wave: 128-byte segments.  Timing what-if without these stores: 1.40 -> 1.27 ms at bs 512)
+          y[(m0 + (j & 3) + 8 * (j >> 2) + 4 * half) * SF_K + 32 * tn + l31] = acc[tn][j];
         if constexpr (STATS) {
           float sm = 0.f;
 #pragma unroll
@@ -2832,9 +2513,6 @@ constexpr int SR_R = 7, SR_ROWF = 728, SR_WO = 112, SR_K = 64;      // ROWF = 24
 constexpr int SR_NX = (SR_R * (SR_ROWF / 4) + 255) / 256, SR_NDY = (SR_WO * SR_K / 4 + 255) / 256;
 
 static inline bool stem_rows_ok(const ssv_conv_desc* d) {
-#ifdef SSV_NO_STEM_ROWS
-  return false;              // diagnostic builds: the gather form everywhere
-#endif
   const int padl = (d->pad * 3 + 3) / 4 * 4, off = padl - d->pad * 3;
   return d->C == 3 && d->K == SR_K && d->R <= SR_R && d->S * 3 <= 24 && d->W % 4 == 0 && d->Wo % 2 == 0 && d->Wo <= SR_WO &&
          padl + d->W * 3 <= SR_ROWF && off + (d->Wo - 1) * d->stride * 3 + 24 <= SR_ROWF && (int64_t)d->N * d->H * d->W * 12 < (1ll << 31);
@@ -3031,7 +2709,7 @@ extern "C" int ssv_gemm_batched_split(int32_t batch, int64_t rows, int32_t C, in
   const bool wide = K >= 128;
   const dim3 grid((unsigned)(cdiv(p.M, 128) * cdiv(K, wide ? 128 : 64)), (unsigned)batch);
   const float* w = nullptr;
-#define BSP(BN_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, BN_, 2, 2, 32, true, false, false, false, false, 0, 0, false, false, SP_>), grid, dim3(256), 0, s, p, a, w, bias, addend, y)
+#define BSP(BN_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, BN_, 2, 2, 32, true, false, false, false, false, 0, 0, false, SP_>), grid, dim3(256), 0, s, p, a, w, bias, addend, y)
   if (C > SP_DUAL_FROM) { if (wide) BSP(128, 2); else BSP(64, 2); }
   else                  { if (wide) BSP(128, 1); else BSP(64, 1); }
 #undef BSP
@@ -3156,11 +2834,3 @@ extern "C" int ssv_conv_arithmetic(const ssv_conv_desc* d, int32_t product) {
   if (product == 2) return (sp_wgrad_ok(d) && !(d->C == 3)) ? SSV_ARITH_BF16X3 : SSV_ARITH_F32_MFMA;
   return sp_dgrad_ok(d) ? SSV_ARITH_BF16X3 : SSV_ARITH_F32_MFMA;      // the strided data-gradient kernel (stride-1 data gradients are forward-kernel launches on the transposed filter)
 }
-
-#ifdef SSV_STAMP
-extern "C" int ssv_debug_stamps(unsigned long long* out_host, int reset) {
-  if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_stamps), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)) != hipSuccess) return -1; }
-  return 0;
-}
-#endif

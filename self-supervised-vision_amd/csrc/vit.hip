@@ -54,7 +54,7 @@ __device__ __forceinline__ void store_tile_T(float* __restrict__ base, int64_t r
 }
 
 // The same tile through a wave-private 32 x 64 float LDS scratch, so that the global stores are whole 256-byte rows (16 lanes x 16 bytes, four rows per
-// instruction) instead of 64 scattered 16-byte pieces: the scattered form is store-ISSUE bound (~7 B / cycle / CU: tools/stamp_attn.py found the 37-token
+// instruction) instead of 64 scattered 16-byte pieces: the scattered form is store-ISSUE bound (~7 B / cycle / CU: round 4's cycle stamps found the 37-token
 // backward spending a quarter of its time issuing dQ stores).  Row c keeps its sixteen 16-byte slots XOR-swizzled with c & 15: the transposing writes and the
 // row-major reads are both free of bank conflicts without padding (the scratch is exactly one tile).  Rows [0, nrows) of the tile are stored.
 __device__ __forceinline__ void store_tile_T_rows(float* __restrict__ scratch, float* __restrict__ base, int64_t row_stride, int row0, int nrows, int lane,
@@ -481,13 +481,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
 // ds_read_b128), which afterwards takes the wave's dQ partial (register-major, so that the reduction reads one b128 per wave and group).
 // 5 products instead of 7 per tile pair; delta = rowsum(O * dO) is formed while the query rows are staged (no extra pass, DELTA is still
 // written for callers that want it).  Per query tile: two barriers (all partials written -> reduce + restage -> next tile).
-#ifdef SSV_STAMP_ATTN   // diagnostic build only (tools/stamp_attn.py): cycles of one wave per phase of a query tile.  Never in the shipped library.
-__device__ unsigned long long g_attn_stamps[16];
-#define ASTAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-                       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); tph[i] += now_ - last_; last_ = now_; } while (0)
-#else
-#define ASTAMP(i) do {} while (0)
-#endif
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 1 : 2, 2))) attn_bwd_fused_k(int T, int heads, const float* __restrict__ Q, const float* __restrict__ K,
                                                             const float* __restrict__ V, int ld, float scale,
@@ -523,7 +516,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
   f32x16 dk_lo = zero16(), dk_hi = zero16(), dv_lo = zero16(), dv_hi = zero16();
   // staging of one query tile: Q and dO rows to registers, delta = sum_d O * dO reduced over the 16 lanes that share a row
   // load_tile only ISSUES the loads (nothing in it depends on a loaded value, so the wave does not wait for them there - the round-3 form computed delta inside it
-  // and paid the global latency once per query tile: 9 % of the tile's cycles, tools/stamp_attn.py); delta is formed when the rows are written to LDS.
+  // and paid the global latency once per query tile: 9 % of the tile's cycles, round 4's cycle stamps); delta is formed when the rows are written to LDS.
   // Workgroups of two waves (T <= 64: four float4 per thread and tensor) do not prefetch: the 48 staging registers spilled, and every reload of a spilled
   // value waits for ALL outstanding loads (s_waitcnt vmcnt(0)) - the prefetch was paid in the middle of the MFMA loops instead of hidden under them.
   constexpr bool PREFETCH = NW > 2;
@@ -564,15 +557,9 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
   if (small_next) load_tile(32, 1);
   __syncthreads();
   float* myscr = scr[wave];
-#ifdef SSV_STAMP_ATTN
-  unsigned long long tph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
   for (int q0 = 0; q0 < T; q0 += 32) {
     const bool more = q0 + 32 < T;
     if (PREFETCH && more) load_tile(q0 + 32);               // next tile's rows fly under this tile's MFMAs
-    ASTAMP(0);
     if (active) {
       float fr[32];
       f32x16 s = zero16(), dp = zero16();
@@ -586,7 +573,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       lds_row32(sd, c, half, fr);
 #pragma unroll
       for (int i = 0; i < 32; ++i) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(fr[i], vreg[i], dp, 0, 0, 0);
-      ASTAMP(1);
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {                         // rows 8 jj + 4 half + {0..3}: their statistics are one ds_read_b128 each
         const f32x4 l4 = *(const f32x4*)&sstat[0][8 * jj + 4 * half], d4 = *(const f32x4*)&sstat[1][8 * jj + 4 * half];
@@ -598,7 +584,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
           dp[j] = p * (dp[j] - d4[e]);                         // dS
         }
       }
-      ASTAMP(2);
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         if (q0 + rowof(j, 0) >= T) continue;                   // padding queries: P and dS are 0
@@ -609,7 +594,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
         dk_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[c], dp[j], dk_lo, 0, 0, 0);
         dk_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[32 + c], dp[j], dk_hi, 0, 0, 0);
       }
-      ASTAMP(3);
       // dS (query on the register index, key on the lane) -> dS^T (key on the register index, query on the lane) through this wave's scratch
 #pragma unroll
       for (int j = 0; j < 16; ++j) myscr[rowof(j, half) * 36 + c] = dp[j];
@@ -619,7 +603,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
         const f32x4 t = *(const f32x4*)(myscr + c * 36 + 8 * jj + 4 * half);
         st_[4 * jj] = t[0]; st_[4 * jj + 1] = t[1]; st_[4 * jj + 2] = t[2]; st_[4 * jj + 3] = t[3];
       }
-      ASTAMP(4);
       f32x16 g_lo = zero16(), g_hi = zero16();
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
@@ -628,7 +611,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
         g_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[c], st_[j], g_lo, 0, 0, 0);
         g_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32 + c], st_[j], g_hi, 0, 0, 0);
       }
-      ASTAMP(5);
       // this wave's dQ partial, group-major: group G = registers 4 G' .. 4 G' + 3 of lo (G < 4) / hi, one b128 per lane and group
 #pragma unroll
       for (int G = 0; G < 4; ++G) {                            // slot of (G, lane): G * 64 + (lane ^ d4), d4 = 2 G + half = the 16-byte piece of the query's row
@@ -636,16 +618,13 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
         *(f32x4*)(myscr + ((G + 4) * 64 + (lane ^ (2 * (G + 4) + half))) * 4) = f32x4{g_hi[4 * G], g_hi[4 * G + 1], g_hi[4 * G + 2], g_hi[4 * G + 3]};
       }
     }
-    ASTAMP(6);
     __syncthreads();                                           // every partial is in LDS; nobody reads sq / sd any more
-    ASTAMP(7);
     // the next tile's rows go to LDS BEFORE this tile's dQ stores are issued: waiting for the (older) prefetched loads must not also wait for younger stores
-    // (vmcnt retires in order; the scattered 16-byte stores take far longer than anything else between the two barriers - tools/stamp_attn.py)
+    // (vmcnt retires in order; the scattered 16-byte stores take far longer than anything else between the two barriers - round 4's cycle stamps)
     if (!PREFETCH && more) {
       if (small_next) store_tile(q0 + 32, 1);
       else { load_tile(q0 + 32); store_tile(q0 + 32); }
     } else if (more) store_tile(q0 + 32);
-    ASTAMP(11);
     // dQ of this query tile: sum over the key tiles in wave order; thread (query q, piece d4) - sixteen lanes store one whole 256-byte row.  The partials'
     // slots are XOR-swizzled (above) so that these row-major reads hit sixteen distinct bank quads.
     for (int i = threadIdx.x; i < 512; i += NW * 64) {
@@ -655,16 +634,8 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       for (int w = 1; w < nact; ++w) acc += *(const f32x4*)(scr[w] + slot);
       if (q0 + q < T) *(f32x4*)(dQ + (tok0 + q0 + q) * ldg + h * DH + 4 * d4) = acc * scale;
     }
-    ASTAMP(8);
     __syncthreads();
-    ASTAMP(9);
   }
-#ifdef SSV_STAMP_ATTN
-  if (lane == 0 && (wave == 0 || wave == 5)) {               // one wave of each SIMD pair's halves; [10] counts the stamped (wave, tile) pairs
-    for (int i = 0; i < 12; ++i) if (i != 10) atomicAdd(&g_attn_stamps[i], tph[i]);
-    atomicAdd(&g_attn_stamps[10], (unsigned long long)((T + 31) / 32));
-  }
-#endif
   // (past the loop's last barrier every dQ partial has been read: the wave's scratch takes its dK, then its dV tile - whole rows to global memory)
   if (active) {
     store_tile_T_rows(myscr, dK + tok0 * ldg + h * DH, ldg, k0, min(32, T - k0), lane, dk_lo, dk_hi, scale);
@@ -1009,7 +980,6 @@ extern "C" int ssv_attention_bwd(int32_t B, int32_t T, int32_t heads, int32_t dh
   SSV_REQUIRE(B <= 65535 && heads <= 65535, "ssv_attention_bwd: grid too large");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(SSV_PROF_ATTN, s);
-#ifndef SSV_ATTN_TWO_PASS          // diagnostic builds only: the two-pass backward for every T
   if (T <= 256) {                   // one pass: a workgroup holds all key tiles of an (image, head), dQ reduced across its waves
     const dim3 grid(1, heads, B);
     if (T <= 64) hipLaunchKernelGGL(attn_bwd_fused_k<2>, grid, dim3(128), 0, s, T, heads, q, k, v, ld, scale, o, dout, ldo, lse, delta, dq, dk, dv, ldg);
@@ -1018,7 +988,6 @@ extern "C" int ssv_attention_bwd(int32_t B, int32_t T, int32_t heads, int32_t dh
     SSV_CHECK_LAUNCH("attn_bwd_fused_k");
     return SSV_OK;
   }
-#endif
   if (T <= 64) {
     const dim3 grid(cdiv(T, 64), heads, B);
     hipLaunchKernelGGL(attn_bwd_dq_k<2>, grid, dim3(128), 0, s, T, heads, q, k, v, ld, scale, o, dout, ldo, lse, delta, dq, ldg);
@@ -1116,11 +1085,3 @@ extern "C" int ssv_vit_embed_bwd(int32_t B, int32_t T, int32_t P3, int32_t E, co
   SSV_CHECK_LAUNCH("vit_embed_bwd_k");
   return SSV_OK;
 }
-
-#ifdef SSV_STAMP_ATTN
-extern "C" int ssv_debug_attn_stamps(unsigned long long* out_host, int reset) {
-  if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_attn_stamps), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_attn_stamps), z, sizeof(z)) != hipSuccess) return -1; }
-  return 0;
-}
-#endif

@@ -1,9 +1,7 @@
 """GPU: 3x3 / stride 1 / padding 1 layers with fewer than 128 output channels (networks/resnet.py:7-10,56-58: conv2 of the 64-channel units, and its data gradient,
-which is the same product with the rotated filter) on the 256 x 64 tile of the forward kernel (csrc/conv_mfma.hip): the shipped generic loader and, with SSV_HIP_LIB
-pointing at a -DSSV_EXP_HALO diagnostic build (tools/exp/r04_halo.sh), the halo loader (conv_fwd_k with C4 == 3), which stages every pixel once per 16-channel chunk
-instead of once per tap.  Against torch fp64 convolutions: plain forward, the statistics epilogue, the data gradient with addend and with the BatchNorm + ReLU gate
-(recomputed and byte-mask) and its partial sums; tiles that start mid-row, span two images, end past M; maps too wide / too narrow for the halo loader's staged
-records.  Tolerances are those of tests/test_gpu_ops.py."""
+which is the same product with the rotated filter) on the 256 x 64 tile of the forward kernel's generic loader (csrc/conv_mfma.hip).  Against torch fp64
+convolutions: plain forward, the statistics epilogue, the data gradient with addend and with the BatchNorm + ReLU gate (recomputed and byte-mask) and its partial
+sums; tiles that start mid-row, span two images, end past M; very wide and very narrow maps.  Tolerances are those of tests/test_gpu_ops.py."""
 import numpy as np
 import pytest
 import torch
@@ -29,7 +27,7 @@ def close(got, ref, rtol=1e-4, what=""):
 
 
 # n, h, w, c, k: 56x56 (a tile = 4.57 rows: every start column, tiles across two images), 32x32 (tiles are whole rows), three chunks, ragged last tile,
-# non-square maps, K below one column tile, a 3-wide map (86 staged rows), and maps the records do not hold (w = 2, w = 96: generic loader)
+# non-square maps, K below one column tile, and very narrow / wide maps (w = 3, 2, 96)
 CASES = [(3, 56, 56, 64, 64), (2, 32, 32, 64, 64), (5, 8, 8, 32, 64), (2, 16, 16, 96, 64), (1, 64, 64, 64, 64), (3, 7, 9, 64, 48), (7, 5, 3, 32, 64), (9, 6, 2, 32, 64),
          (1, 4, 96, 32, 64), (1, 1, 1, 64, 64)]
 

@@ -31,7 +31,7 @@ SCOPE_EXCEPTIONS = {"ssv_linear_fwd_gelugrad"}
 
 # template-argument count of the GEMM kernels whose LAST argument is SP (csrc/conv_mfma.hip): true = the launch multiplies in SSV_ARITH_BF16X3 (six bf16 piece
 # products per fp32 product on v_mfma_f32_16x16x32_bf16), false = on v_mfma_f32_32x32x2_f32
-_SP_ARGS = {"conv_fwd_k": 15, "conv_wgrad_k": 12, "conv_dgrad_k": 8}
+_SP_ARGS = {"conv_fwd_k": 14, "conv_wgrad_k": 12, "conv_dgrad_k": 8}
 
 
 def is_bf16x3(name):
