@@ -589,6 +589,28 @@ int ssv_queue_push(int32_t K, int32_t D, float* bank, int32_t ptr, int32_t n, co
 /* The same push with the queue pointer in device memory (read by the kernel, advanced behind it): no launch argument changes from step to step (HIP-graph replay). */
 int ssv_queue_push_counted(int32_t K, int32_t D, float* bank, int32_t* ptr_dev, int32_t n, const float* keys, float eps, void* stream);
 
+/* ---- PIRL (models/pirl.py, utils/losses.py:92-117): a per-sample memory bank [N][D] in device memory, read and written BY INDEX (int64 indices) ----
+ * PirlLoss, forward and backward in one call.  With m_i = bank[pos_index[i]], v = the features (divided by max(|z|, 1e-12) when normalize),
+ * n_ik = m_i . bank[neg_index[k]] * inv_temp and L_i = logsumexp_k n_ik:
+ *   loss = mean_i [ w (lse(p1_i, L_i) - p1_i) + (1 - w) (lse(p2_i, L_i) - p2_i) ],   p1_i = m_i . v_patch_i * inv_temp,   p2_i = m_i . v_img_i * inv_temp
+ * d_img / d_patch [B][D] receive d loss / d (raw features).  The B x K logits are formed tile by tile on the fp32 MFMA instruction from bank rows gathered by
+ * index inside the kernel and reduced on the fly: neither they nor any copy of bank rows reach memory.  K is cut into `splits` runs (0: the library's choice,
+ * otherwise clamped to [1, min(64, tiles of 32 negatives)]); their partial (max, sum) pairs are folded in split order, so equal inputs give equal bits.
+ * D must be a multiple of 4, at most 512; bank 16-byte aligned; ws 256-byte aligned, at least the workspace size for the LARGEST split count the call may
+ * take (64 is always enough).  An index outside [0, N) is never dereferenced: the entry is left out and the first int32 of ws is set non-zero (0 otherwise). */
+int64_t ssv_pirl_default_splits(int32_t B, int32_t K);
+size_t ssv_pirl_loss_workspace_bytes(int32_t B, int32_t splits);
+int ssv_pirl_loss_fwd_bwd(int64_t N, int32_t D, int32_t B, int32_t K, const float* bank, const void* pos_index, const void* neg_index,
+                          const float* img_features, const float* patch_features, int32_t normalize, float inv_temp, float loss_weight,
+                          int32_t splits, float* loss, float* d_img, float* d_patch, void* ws, size_t ws_bytes, void* stream);
+/* MemoryBank.update_vectors (models/pirl.py:37-39): bank[index[i]] = momentum * bank[index[i]] + (1 - momentum) * z[i] / max(|z[i]|, eps) for i < n, not
+ * re-normalised.  momentum = 0 on a zero bank is initialize_vectors (:33-35).  The indices of one call must be DISTINCT (a batch sampled without replacement):
+ * rows are updated concurrently.  An index outside [0, N) is skipped. */
+int ssv_bank_momentum_update(int64_t N, int32_t D, float* bank, int32_t n, const void* index, const float* z, float momentum, float eps, void* stream);
+/* The jigsaw cut (models/pirl.py:67-71): x [B][H][W][C] -> out [P][B][patch][patch][C], P = (W / patch) (H / patch), patch p = xi * (H / patch) + yi holding
+ * rows yi * patch .. and columns xi * patch .. of every image (the reference loops x outside y); every patch is a dense NHWC batch of its own. */
+int ssv_patch_split(int32_t B, int32_t H, int32_t W, int32_t C, int32_t patch, const float* x, float* out, void* stream);
+
 /* linear probe (utils/eval_utils.py:37-76): NLLLoss(log_softmax(logits)) and accuracy of a [N][ld] logit matrix (first C columns
  * valid) against int32 labels; stats[0] = mean loss, stats[1] = fraction of rows whose arg-max is the label; dlogits (may be NULL)
  * = d(mean loss)/dlogits, padding columns zeroed.  Workspace: ssv_softmax_ce_workspace_bytes(N). */

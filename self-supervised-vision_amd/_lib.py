@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSV_HIP_LIB") or os.path.join(_HERE, "csrc", "libssv_hip.so")   # override: diagnostic builds only
 
-ABI_VERSION = 120        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
+ABI_VERSION = 121        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
 PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_fwd", "bn_bwd", "pool", "loss", "optim", "aug", "misc", "attn", "norm")
 
 
@@ -185,6 +185,11 @@ SIGNATURES = {
     "ssv_moco_loss_fwd_bwd": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
     "ssv_queue_push": (C.c_int, [_i32, _i32, _vp, _i32, _i32, _vp, _f32, _vp]),
     "ssv_queue_push_counted": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _f32, _vp]),
+    "ssv_pirl_default_splits": (_i64, [_i32, _i32]),
+    "ssv_pirl_loss_workspace_bytes": (_sz, [_i32, _i32]),
+    "ssv_pirl_loss_fwd_bwd": (C.c_int, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ssv_bank_momentum_update": (C.c_int, [_i64, _i32, _vp, _i32, _vp, _vp, _f32, _f32, _vp]),
+    "ssv_patch_split": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ssv_softmax_ce_workspace_bytes": (_sz, [_i32]),
     "ssv_softmax_ce_fwd_bwd": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssv_sgd": (C.c_int, [_i64, _vp, _vp, _vp, _f32, _f32, _f32, C.c_int, C.c_int, _vp]),

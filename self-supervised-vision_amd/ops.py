@@ -998,6 +998,60 @@ def queue_push_counted(bank, queue_size, pointer_dev, keys, eps=1e-12):
     call("ssv_queue_push_counted", int(queue_size), bank.shape[1], ptr(bank), ptr(pointer_dev), keys.shape[0], ptr(keys), float(eps), stream())
 
 
+# K splits of the PIRL loss kernel: None = the library's choice (ssv_pirl_default_splits), an integer forces it (diagnostic switch, set from Python: 1 = every row
+# block sweeps all negatives in one workgroup, 64 = the most the kernel takes; the library clamps it to the number of 32-negative tiles)
+PIRL_SPLITS = None
+
+
+def pirl_splits():
+    return 0 if PIRL_SPLITS is None else max(1, min(int(PIRL_SPLITS), 64))
+
+
+def pirl_loss(bank, pos_index, neg_index, img_features, patch_features, normalize, inv_temp, loss_weight, splits=None):
+    """PirlLoss forward + backward against the device bank [N, D], read by index (int64 [B] positives, int64 [K] negatives).
+    Returns (loss 0-d, d img_features, d patch_features, flag): flag is a one-element int32 tensor, non-zero when an index fell outside [0, N) -
+    check_pirl_flag turns it into an error."""
+    _lib._dev(bank, pos_index, neg_index, img_features, patch_features)
+    if pos_index.dtype != torch.int64 or neg_index.dtype != torch.int64:
+        raise _lib.SsvError("pirl_loss: indices must be int64")
+    b, d = img_features.shape
+    if patch_features.shape != img_features.shape or bank.dim() != 2 or bank.shape[1] != d or pos_index.numel() != b or not bank.is_contiguous():
+        raise _lib.SsvError(f"pirl_loss: features {tuple(img_features.shape)} / {tuple(patch_features.shape)}, bank {tuple(bank.shape)}, {pos_index.numel()} positives do not fit together")
+    splits = pirl_splits() if splits is None else int(splits)
+    loss = torch.empty((), dtype=torch.float32, device=bank.device)
+    dimg, dpatch = torch.empty_like(img_features), torch.empty_like(patch_features)
+    ws = workspace.get(_lib.load().ssv_pirl_loss_workspace_bytes(b, 64), bank.device)
+    call("ssv_pirl_loss_fwd_bwd", bank.shape[0], d, b, neg_index.numel(), ptr(bank), ptr(pos_index), ptr(neg_index), ptr(img_features), ptr(patch_features),
+         int(bool(normalize)), float(inv_temp), float(loss_weight), splits, ptr(loss), ptr(dimg), ptr(dpatch), ptr(ws), ws.numel(), stream())
+    return loss, dimg, dpatch, ws[:4].view(torch.int32).clone()         # the workspace is reused by the next call: the flag word leaves it now
+
+
+def check_pirl_flag(flag):
+    if int(flag.item()) != 0:
+        raise _lib.SsvError("pirl_loss: a positive or negative index lies outside the memory bank (the entry was left out of the loss)")
+
+
+def bank_momentum_update(bank, index, z, momentum, eps=1e-12):
+    """bank[index[i]] = momentum * bank[index[i]] + (1 - momentum) * z[i] / max(|z[i]|, eps); the indices of one call are distinct."""
+    _lib._dev(bank, index, z)
+    if index.dtype != torch.int64 or z.shape != (index.numel(), bank.shape[1]) or not (bank.is_contiguous() and z.is_contiguous()):
+        raise _lib.SsvError(f"bank_momentum_update: int64 [n] indices and dense [n, {bank.shape[1]}] features expected")
+    call("ssv_bank_momentum_update", bank.shape[0], bank.shape[1], ptr(bank), index.numel(), ptr(index), ptr(z), float(momentum), float(eps), stream())
+    return bank
+
+
+def patch_split(x, patch):
+    """[B,C,H,W] (NCHW or channels_last) -> [P,B,C,patch,patch], every patch[p] a channels_last batch of its own (what the encoders take without a copy);
+    p = xi * (H / patch) + yi - the reference's loop order (models/pirl.py:67-71)."""
+    nhwc = nchw_to_nhwc(x)
+    b, h, w, c = nhwc.shape
+    if h % patch or w % patch:
+        raise _lib.SsvError(f"patch_split: {patch} does not divide {h} x {w}")
+    out = _empty(((h // patch) * (w // patch), b, patch, patch, c), nhwc)
+    call("ssv_patch_split", b, h, w, c, int(patch), ptr(nhwc), ptr(out), stream())
+    return out.permute(0, 1, 4, 2, 3)
+
+
 def linear_gelu_fwd(x, w, bias, keep_h=True):
     """(h, gelu(h)) with h = x w^T + bias, both written by one GEMM epilogue.  x [M, C] dense, w [K, C].  ``keep_h`` False (a forward without
     a backward): only gelu(h) is written and h comes back as None."""

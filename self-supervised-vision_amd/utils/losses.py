@@ -299,3 +299,38 @@ class MocoLoss(nn.Module):
     def forward(self, query, keys, memory_vectors, queue_size=None):
         k = memory_vectors.shape[0] if queue_size is None else queue_size
         return _MocoFn.apply(query, keys, memory_vectors, k, self.normalize, self.temperature)
+
+
+class _PirlFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img_features, patch_features, bank, pos_index, neg_index, module):
+        # one launch sequence gives the loss and both gradients (the negatives' logits are bank-row products: constants); backward only scales them
+        loss, dimg, dpatch, module.last_flag = ops.pirl_loss(bank, pos_index, neg_index, img_features.detach().contiguous(), patch_features.detach().contiguous(),
+                                                             module.normalize, 1.0 / float(module.temp), module.loss_weight)
+        ctx.saved = (dimg, dpatch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dimg, dpatch = ctx.saved
+        g = dloss.contiguous()
+        return ops.scale_(dimg, g), ops.scale_(dpatch, g), None, None, None, None
+
+
+class PirlLoss(nn.Module):
+    """utils/losses.py:92-117 against the DEVICE memory bank: instead of the gathered positive / negative rows, ``forward`` takes the bank [N, D] and the
+    int64 index vectors (``pos_index`` [B]: the batch's own rows, ``neg_index`` [K]) - the rows are gathered inside the loss kernel.  An index outside the
+    bank raises SsvError: at once (``check=True``, one host synchronisation), or when the caller hands ``last_flag`` to ops.check_pirl_flag."""
+
+    def __init__(self, normalize=True, temperature=1.0, loss_weight=0.5):
+        super().__init__()
+        self.loss_weight, self.normalize, self.temp = loss_weight, normalize, temperature
+        self.last_flag = None
+
+    def forward(self, img_features, patch_features, bank, pos_index, neg_index, check=True):
+        if hdist.is_on():
+            raise NotImplementedError("PirlLoss is single-process: the memory bank is not replicated across ranks")
+        loss = _PirlFn.apply(img_features, patch_features, bank, pos_index, neg_index, self)
+        if check:
+            ops.check_pirl_flag(self.last_flag)
+        return loss
