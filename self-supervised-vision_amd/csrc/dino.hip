@@ -63,10 +63,12 @@ __global__ void __launch_bounds__(256) dino_student_k(int V, int K, const float*
   float sm = 0.f;
   for (int k = threadIdx.x; k < K; k += 256) sm += expf(srow[k] * inv_temp_s - mx);
   sm = block_sum(sm, sh);
-  const float lse = mx + logf(sm);
+  // log p = (s - max) - log(sum): the maximum and log(sum) are kept apart.  Folded into one lse = max + log(sum), the sum is rounded at the size of the
+  // maximum (logits of 300 at an input scale of 8 / temp 0.1: 1.5e-5) and every exp(log p) of the row carries that as a relative error.
+  const float lsm = logf(sm);
   float acc = 0.f;
   for (int k = threadIdx.x; k < K; k += 256) {
-    const float logp = srow[k] * inv_temp_s - lse;
+    const float logp = (srow[k] * inv_temp_s - mx) - lsm;
     const float tt = trow[k];
     acc -= tt * logp;
     dstudent[row * K + k] = gscale * (2.f * expf(logp) - tt);
