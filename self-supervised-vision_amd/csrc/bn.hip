@@ -773,7 +773,7 @@ extern "C" int ssv_bn_relu_maxpool_bwd(int32_t N, int32_t H, int32_t W, int32_t 
   float* k2 = k1 + C;
   const dim3 grid(p.nblk, p.GY);
   int nred = p.nblk;
-  if (xmax && bn_plan((int64_t)N * Ho * Wo, C).nblk > p.nblk) xmax = nullptr;      // the pooled plan's partials must fit the workspace laid out above (they do but for tiny maps)
+  if (xmax && bn_plan((int64_t)N * Ho * Wo, C).nblk > p.nblk) xmax = nullptr;      // the pooled plan's partials must fit the workspace laid out above (they do unless rounding gives the pooled plan more blocks: 449 x 11 x 11 x 256 has 1011 against 1007)
   if (xmax) {
     // Reduction at the POOLED resolution (round 4): sum g and sum g * xhat over the 112^2 map are sums over the pooled positions - a pixel's g is the sum of
     // the dpool of the windows whose arg-max it is, gated by the ReLU bit of that pixel, and the forward kept the raw conv output of every window's arg-max
