@@ -1678,6 +1678,24 @@ ConvKP make_kp(const ssv_conv_desc* d) {
   return p;
 }
 
+// The weight gradient's split over the rows of its contraction: as many chunks as one resident round of workgroups holds, in whole K-steps.
+struct RowSplit { int nsplit, chunk; };
+RowSplit wgrad_row_split(int bm, int64_t tiles, int64_t rows, int max_chunk = 0) {
+  // one resident round: 3 workgroups per CU for the 128-row kernels, 4 for the 64-row ones.  Round DOWN - one workgroup more
+  // than the chip holds costs a whole second round for the stragglers.
+  const int slots = bm == 128 ? 768 : 1024;
+  int64_t ns = slots / tiles;
+  const int64_t max_by_rows = cdiv64(rows, 256);
+  if (ns > max_by_rows) ns = max_by_rows;
+  if (ns < 1) ns = 1;
+  int64_t chunk = cdiv64(cdiv64(rows, ns), 32) * 32;     // whole K-steps for both BK = 16 and 32
+  if (max_chunk > 0 && chunk > max_chunk) {              // blocked accumulation: no fp32 chain longer than max_chunk rows; equal chunks
+    const int64_t nb = cdiv64(rows, (int64_t)max_chunk);
+    chunk = cdiv64(cdiv64(rows, nb), 32) * 32;
+  }
+  return {(int)cdiv64(rows, chunk), (int)chunk};
+}
+
 struct WgradPlan { int bm, bn, it, jt, nsplit, chunk; };
 WgradPlan plan_wgrad(const ssv_conv_desc* d, int groups = 0) {
   WgradPlan w;
@@ -1694,25 +1712,27 @@ WgradPlan plan_wgrad(const ssv_conv_desc* d, int groups = 0) {
     const int per_row = cdiv((cdiv(w.bm, kg) + 1) * cg, w.bn) + 1;
     tiles = w.it * d->R * d->S * (per_row < d->C / w.bn ? per_row : d->C / w.bn);
   }
-  // one resident round: 3 workgroups per CU for the 128-row kernels, 4 for the 64-row ones.  Round DOWN - one workgroup more
-  // than the chip holds costs a whole second round for the stragglers.
-  const int slots = w.bm == 128 ? 768 : 1024;
-  int64_t ns = slots / tiles;
-  const int64_t max_by_rows = cdiv64(M, 256);
-  if (ns > max_by_rows) ns = max_by_rows;
-  if (ns < 1) ns = 1;
-  int64_t chunk = cdiv64(cdiv64(M, ns), 32) * 32;     // whole K-steps for both BK = 16 and 32
-  w.chunk = (int)chunk;
-  w.nsplit = (int)cdiv64(M, chunk);
+  const RowSplit rs = wgrad_row_split(w.bm, tiles, M);
+  w.chunk = rs.chunk; w.nsplit = rs.nsplit;
   return w;
 }
 
 }  // namespace
 
 // ---- launch selection (compile-time variants only: no environment, no global state) ---------------------------
-// K-step 32 when the contraction's channel count allows it, else 16; tile by output width.
+// K-step 32 when the contraction's channel count allows it, else 16; tile by output width.  One selection function per kernel family (fwd_tile,
+// dgrad_tile, plan_wgrad) says which tile and arithmetic a launch takes; every launch site AND every group-count / workspace query of the family
+// asks it, and one dispatcher per family (fwd_launch, dgrad_launch, wgrad_launch) turns its answer into template arguments.
 namespace {
 
+// run-time value -> compile-time tag: f(ic<V>) for the first V of the list that equals v, for the LAST one if none does
+template <int V> using ic = std::integral_constant<int, V>;
+template <int V0, int... Vs, class F>
+inline void for_value(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(ic<V0>{});
+  else if (v == V0) f(ic<V0>{});
+  else for_value<Vs...>(v, f);
+}
 
 // Does a forward-kernel launch described by d run its bf16-piece variant (SSV_ARITH_BF16X3)?  The float4 path with whole 32-channel k-tiles, 16-byte output rows, a
 // pre-split weight operand (a block-diagonal bank included: its tiles contract over their own groups' channels in either arithmetic).
@@ -1721,7 +1741,7 @@ namespace {
 inline bool sp_planes_fit(const ssv_conv_desc* d) {
   return (int64_t)d->K * d->R * d->S * d->C * 6 < (1ll << 31);
 }
-inline bool sp_fwd_ok(const ssv_conv_desc* d, int groups = 0) {
+inline bool sp_fwd_ok(const ssv_conv_desc* d) {
   return d->arithmetic == SSV_ARITH_BF16X3 && d->w_planes != nullptr && (((uintptr_t)d->w_planes) & 15) == 0 && d->C % 32 == 0 && d->K % 4 == 0 &&
          sp_planes_fit(d);
 }
@@ -1729,8 +1749,8 @@ inline bool sp_fwd_ok(const ssv_conv_desc* d, int groups = 0) {
 // unfused variant of a layer takes the same form, so they stay bit-identical).  Measured on the 53 ResNet-50 layers (tests/test_gpu_split.py): with one accumulator
 // the error against fp64 is 0.8-1.0x the fp32-MFMA kernel's up to a contraction of 1,152 and 1.05-1.07x from 2,048 on.
 constexpr int SP_DUAL_FROM = 1152;
-inline int sp_fwd_mode(const ssv_conv_desc* d, int groups = 0) {
-  if (!sp_fwd_ok(d, groups)) return 0;
+inline int sp_fwd_mode(const ssv_conv_desc* d) {
+  if (!sp_fwd_ok(d)) return 0;
   return (int64_t)d->R * d->S * d->C > SP_DUAL_FROM ? 2 : 1;
 }
 // the strided data-gradient kernel: its 128 x 128 tile (C >= 128), whole 32-channel k-tiles of the output channels, the weights pre-split
@@ -1738,8 +1758,53 @@ inline bool sp_dgrad_ok(const ssv_conv_desc* d) {
   return d->arithmetic == SSV_ARITH_BF16X3 && d->w_planes != nullptr && (((uintptr_t)d->w_planes) & 15) == 0 && d->K % 32 == 0 && d->C >= 128 && d->C % 8 == 0 &&
          sp_planes_fit(d);
 }
-inline bool sp_wgrad_ok(const ssv_conv_desc* d, int groups = 0) {
+inline bool sp_wgrad_ok(const ssv_conv_desc* d) {
   return d->arithmetic == SSV_ARITH_BF16X3 && d->C % 4 == 0 && d->K % 4 == 0;
+}
+
+// The forward kernel's tile and arithmetic (sp: 0 fp32 MFMA, 1 / 2 bf16 pieces with one / two accumulators) and the x extent of its grid.
+// The bf16-piece variants take 128 rows at every width.
+struct FwdTile { int bm, bn, sp; unsigned grid_x; };
+inline FwdTile fwd_tile(const ssv_conv_desc* d, int groups = 0) {
+  FwdTile t;
+  t.sp = sp_fwd_mode(d);
+  const bool wide = d->K >= 128 && groups <= 1;               // block-diagonal banks: the 64-column tile sees the fewest foreign groups
+  // (1x1 layers with few k-tiles - 64 -> 256 at 56x56 runs at 2.7 TB/s and 69 TFLOP/s, the SUM of its MFMA and HBM times - were tried on a 128 x 64 tile
+  //  at 4 / 5 workgroups per CU, on a 64 x 256 tile writing whole 1 KB rows and as a persistent kernel that loads its next tile under the epilogue: no change, r03 x3)
+  // (3x3 / stride 1 / padding 1 on the 256 x 64 tile, round 4: a halo loader that stages every pixel once per channel chunk instead of once per tap, with one or
+  //  two LDS stages, lands on 104-109 TFLOP/s like the generic loader - the kernel already keeps the matrix pipe 0.80-0.82 busy and the chip clocks it at
+  //  2.0-2.1 GHz under that load; profiles/r04_probe_halo_loader.txt)
+  t.bm = (wide || t.sp) ? 128 : 256;
+  t.bn = wide ? 128 : 64;
+  t.grid_x = (unsigned)(cdiv64((int64_t)d->N * d->Ho * d->Wo, t.bm) * cdiv(d->K, t.bn));
+  return t;
+}
+
+// Which arithmetics a call site's variants exist in: both, fp32 MFMA only, bf16 pieces only.
+enum { ARITH_ANY, ARITH_F32, ARITH_SPLIT };
+
+struct FwdArgs { FwdTile t; unsigned batch; hipStream_t s; const ConvKP* p; const float* x; const float* w; const float* bias; const float* addend; float* y; };
+
+// The float4 path of the forward kernel on the tile and arithmetic of a.t; the caller gives the variant in conv_fwd_k's own parameter order.  The compact
+// stride-2 addend and the GELU epilogues exist on the 128 x 128 tile only (their entry points require K >= 128), the tap-vector gather of the padded
+// stems and K-step 16 on fp32 MFMA only (C % 32 != 0 there, so a.t.sp is 0).
+template <int BK, int EPI = 0, bool STATS = false, int C4 = 0, bool XF = false, int GATE = 0, int OPM = 0, bool ADDS2 = false,
+          int ARITH = (C4 != 0 || BK != 32) ? ARITH_F32 : ARITH_ANY>
+inline void fwd_launch(const FwdArgs& a) {
+  constexpr bool wide_only = ADDS2 || EPI != 0;
+  auto arith = [&](auto SP) {
+    auto tile = [&](auto BM, auto BN, auto WGM, auto WGN) {
+      hipLaunchKernelGGL((conv_fwd_k<decltype(BM)::value, decltype(BN)::value, decltype(WGM)::value, decltype(WGN)::value, BK, true, EPI, STATS, C4, XF, GATE, OPM, ADDS2, decltype(SP)::value>),
+                         dim3(a.t.grid_x, a.batch), dim3(256), 0, a.s, *a.p, a.x, a.w, a.bias, a.addend, a.y);
+    };
+    if (wide_only || a.t.bn == 128) tile(ic<128>{}, ic<128>{}, ic<2>{}, ic<2>{});
+    else if constexpr (wide_only) {}
+    else if constexpr (decltype(SP)::value != 0) tile(ic<128>{}, ic<64>{}, ic<2>{}, ic<2>{});
+    else tile(ic<256>{}, ic<64>{}, ic<4>{}, ic<1>{});
+  };
+  if constexpr (ARITH == ARITH_F32) for_value<0>(a.t.sp, arith);
+  else if constexpr (ARITH == ARITH_SPLIT) for_value<2, 1>(a.t.sp, arith);
+  else for_value<2, 1, 0>(a.t.sp, arith);
 }
 
 // forward family: optional statistics epilogue (pmean / pm2) and optional fused input BatchNorm + ReLU (in_scale / in_shift)
@@ -1750,64 +1815,25 @@ int launch_fwd(const ssv_conv_desc* d, const float* x, const float* w, const flo
   p.add_H2 = add_H2; p.add_W2 = add_W2;
   p.aux_out = pmean; p.aux_out2 = pm2; p.xf_scale = in_scale; p.xf_shift = in_shift;
   if (groups > 1) { p.Cg = d->C / groups; p.Kg = d->K / groups; }
+  if (gate) p.gate = *gate;
   const bool stats = pmean != nullptr, xf = in_scale != nullptr;
-  const int sp = sp_fwd_mode(d, groups);
-  const bool wide = d->K >= 128 && groups <= 1;               // block-diagonal banks: the 64-column tile sees the fewest foreign groups
-  // (1x1 layers with few k-tiles - 64 -> 256 at 56x56 runs at 2.7 TB/s and 69 TFLOP/s, the SUM of its MFMA and HBM times - were tried on a 128 x 64 tile
-  //  at 4 / 5 workgroups per CU, on a 64 x 256 tile writing whole 1 KB rows and as a persistent kernel that loads its next tile under the epilogue: no change, r03 x3)
-  const unsigned grid = (unsigned)(wide ? cdiv(p.M, 128) * cdiv(d->K, 128) : (sp ? cdiv(p.M, 128) : cdiv(p.M, 256)) * cdiv(d->K, 64));
-  // (3x3 / stride 1 / padding 1 on the 256 x 64 tile, round 4: a halo loader that stages every pixel once per channel chunk instead of once per tap, with one or
-  //  two LDS stages, lands on 104-109 TFLOP/s like the generic loader - the kernel already keeps the matrix pipe 0.80-0.82 busy and the chip clocks it at
-  //  2.0-2.1 GHz under that load; profiles/r04_probe_halo_loader.txt)
+  const FwdArgs a = {fwd_tile(d, groups), 1, s, &p, x, w, bias, addend, y};
   if (gate) {                                                  // C % 32 == 0 checked by the caller
-    p.gate = *gate;
-#define FWDG_(BM_, BN_, WM_, WN_, G_, SP_) \
-  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, false, false, false, G_, 0, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
-#define FWDG(BM_, BN_, WM_, WN_, G_) FWDG_(BM_, BN_, WM_, WN_, G_, 0)
-#define FWDG_TILE(G_) do { if (sp == 2) { if (wide) FWDG_(128, 128, 2, 2, G_, 2); else FWDG_(128, 64, 2, 2, G_, 2); } \
-                           else if (sp) { if (wide) FWDG_(128, 128, 2, 2, G_, 1); else FWDG_(128, 64, 2, 2, G_, 1); } \
-                           else    { if (wide) FWDG(128, 128, 2, 2, G_); else FWDG(256, 64, 4, 1, G_); } } while (0)
-    if (add_H2 > 0) {                                          // compact stride-2 addend: wide tile, byte-mask gates (checked by the caller)
-#define FWDGS_(G_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false, G_, 0, true, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
-#define FWDGS(G_) do { if (sp == 2) FWDGS_(G_, 2); else if (sp) FWDGS_(G_, 1); else FWDGS_(G_, 0); } while (0)
-      if (gate->x2) FWDGS(3); else FWDGS(2);
-#undef FWDGS
-#undef FWDGS_
-    } else if (gate->x2) FWDG_TILE(3); else if (gate->mask) FWDG_TILE(2); else FWDG_TILE(1);
-#undef FWDG_TILE
-#undef FWDG
-#undef FWDG_
-    return SSV_OK;
+    const int gm = gate->x2 ? 3 : (gate->mask ? 2 : 1);
+    if (add_H2 > 0) for_value<3, 2>(gm, [&](auto G) { fwd_launch<32, 0, false, 0, false, decltype(G)::value, 0, true>(a); });   // compact stride-2 addend: wide tile, byte-mask gates (checked by the caller)
+    else for_value<3, 2, 1>(gm, [&](auto G) { fwd_launch<32, 0, false, 0, false, decltype(G)::value>(a); });
   }
-#define FWD_(BM_, BN_, WM_, WN_, BK_, ST_, C4_, XF_, SP_) \
-  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, BK_, true, false, ST_, C4_, XF_, 0, 0, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, addend, y)
-#define FWD(BM_, BN_, WM_, WN_, BK_, ST_, C4_, XF_) FWD_(BM_, BN_, WM_, WN_, BK_, ST_, C4_, XF_, 0)
-// the float4 path with K-step 32: either arithmetic
-#define FWD_TILE_A(ST_, XF_) do { \
-    if (sp == 2) { if (wide) FWD_(128, 128, 2, 2, 32, ST_, 0, XF_, 2); else FWD_(128, 64, 2, 2, 32, ST_, 0, XF_, 2); } \
-    else if (sp) { if (wide) FWD_(128, 128, 2, 2, 32, ST_, 0, XF_, 1); else FWD_(128, 64, 2, 2, 32, ST_, 0, XF_, 1); } \
-    else    { if (wide) FWD_(128, 128, 2, 2, 32, ST_, 0, XF_, 0); else FWD_(256, 64, 4, 1, 32, ST_, 0, XF_, 0); } } while (0)
-#define FWD_TILE(BK_, ST_, C4_, XF_) do { if (wide) FWD(128, 128, 2, 2, BK_, ST_, C4_, XF_); else FWD(256, 64, 4, 1, BK_, ST_, C4_, XF_); } while (0)
-  if (stats && d->C == 4) {                                    // the padded image stem with the statistics epilogue
-    FWD_TILE(32, true, true, false);
-  } else if (stats || xf) {                                    // C % 32 == 0 checked by the callers
-    if (stats && xf) FWD_TILE_A(true, true);
-    else if (stats)  FWD_TILE_A(true, false);
-    else             FWD_TILE_A(false, true);
-  } else if (d->C == 4) {                                      // image stems (3 channels padded to 4): tap-vector gather
-    FWD_TILE(32, false, true, false);
-  } else if (d->C % 32 == 0) {
-    FWD_TILE_A(false, false);
-  } else if (d->C % 16 == 0) {
-    FWD_TILE(16, false, false, false);
-  } else {
+  else if (stats && d->C == 4) fwd_launch<32, 0, true, 1>(a);          // the padded image stem with the statistics epilogue
+  else if (stats && xf) fwd_launch<32, 0, true, 0, true>(a);           // stats || xf: C % 32 == 0 checked by the callers
+  else if (stats) fwd_launch<32, 0, true>(a);
+  else if (xf) fwd_launch<32, 0, false, 0, true>(a);
+  else if (d->C == 4) fwd_launch<32, 0, false, 1>(a);                  // image stems (3 channels padded to 4): tap-vector gather
+  else if (d->C % 32 == 0) fwd_launch<32>(a);                          // the float4 path with K-step 32: either arithmetic
+  else if (d->C % 16 == 0) fwd_launch<16>(a);
+  else {                                                               // scalar gather: 128 x 64 at every width
     const unsigned g2 = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 64));
     hipLaunchKernelGGL((conv_fwd_k<128, 64, 2, 2, GBK, false>), dim3(g2), dim3(256), 0, s, p, x, w, bias, addend, y);
   }
-#undef FWD_TILE
-#undef FWD_TILE_A
-#undef FWD
-#undef FWD_
   return SSV_OK;
 }
 
@@ -1867,7 +1893,7 @@ int check_gate(const ssv_bn_gate* g, const char* who) {
 extern "C" int64_t ssv_conv2d_fwd_gate_groups(const ssv_conv_desc* d) {
   if (!d || d->K <= 0) return 0;
   const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-  const int bm = (d->K >= 128 || sp_fwd_ok(d)) ? 128 : 256;           // rows of the launch's tile (the bf16-piece variants: 128 at every width)
+  const int bm = fwd_tile(d).bm;                                      // rows of the launch's tile
   return cdiv64(M, bm) * (bm / 64);
 }
 
@@ -1921,26 +1947,10 @@ int fwd_dyin_impl(const ssv_conv_desc* d, const float* g, const ssv_bn_dyin* dyi
   p.dyin_x = dyin->x; p.dyin_coef = dyin->coef;
   p.add_H2 = add_H2; p.add_W2 = add_W2;
   if (gate) p.gate = *gate;
-  const bool wide = d->K >= 128;
-  const int sp = sp_fwd_mode(d);
-  const unsigned grid = (unsigned)(wide ? cdiv(p.M, 128) * cdiv(d->K, 128) : (sp ? cdiv(p.M, 128) : cdiv(p.M, 256)) * cdiv(d->K, 64));
+  const FwdArgs a = {fwd_tile(d), 1, s, &p, g, w, nullptr, addend, y};
   const int gm = gate ? (gate->x2 ? 3 : (gate->mask ? 2 : 1)) : 0;
-#define FWDD_(BM_, BN_, WM_, WN_, G_, SP_) \
-  hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, false, false, false, G_, 1, false, SP_>), dim3(grid), dim3(256), 0, s, p, g, w, (const float*)nullptr, addend, y)
-#define FWDD(BM_, BN_, WM_, WN_, G_) FWDD_(BM_, BN_, WM_, WN_, G_, 0)
-#define FWDD_TILE(G_) do { if (sp == 2) { if (wide) FWDD_(128, 128, 2, 2, G_, 2); else FWDD_(128, 64, 2, 2, G_, 2); } \
-                           else if (sp) { if (wide) FWDD_(128, 128, 2, 2, G_, 1); else FWDD_(128, 64, 2, 2, G_, 1); } \
-                           else    { if (wide) FWDD(128, 128, 2, 2, G_); else FWDD(256, 64, 4, 1, G_); } } while (0)
-  if (add_H2 > 0) {                                          // compact stride-2 addend: wide tile and byte-mask gate checked by the caller
-#define FWDDS_(G_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false, G_, 1, true, SP_>), dim3(grid), dim3(256), 0, s, p, g, w, (const float*)nullptr, addend, y)
-#define FWDDS(G_) do { if (sp == 2) FWDDS_(G_, 2); else if (sp) FWDDS_(G_, 1); else FWDDS_(G_, 0); } while (0)
-    if (gm == 3) FWDDS(3); else FWDDS(2);
-#undef FWDDS
-#undef FWDDS_
-  } else if (gm == 3) FWDD_TILE(3); else if (gm == 2) FWDD_TILE(2); else if (gm == 1) FWDD_TILE(1); else FWDD_TILE(0);
-#undef FWDD_TILE
-#undef FWDD
-#undef FWDD_
+  if (add_H2 > 0) for_value<3, 2>(gm, [&](auto G) { fwd_launch<32, 0, false, 0, false, decltype(G)::value, 1, true>(a); });   // compact stride-2 addend: wide tile and byte-mask gate checked by the caller
+  else for_value<3, 2, 1, 0>(gm, [&](auto G) { fwd_launch<32, 0, false, 0, false, decltype(G)::value, 1>(a); });
   SSV_CHECK_LAUNCH("ssv_conv2d_fwd_dyin");
   return SSV_OK;
 }
@@ -1979,14 +1989,7 @@ extern "C" int ssv_conv2d_fwd_sumin_stats(const ssv_conv_desc* d, const float* x
   p.sum_res = res; p.sum_scale = scale; p.sum_shift = shift; p.sum_rscale = rscale; p.sum_rshift = rshift; p.sum_out = a_out; p.sum_mask = mask_out;
   // (a 128 x 64 tile with K-step 64 - 256-byte row pieces - is 6 % faster for the 256 -> 64 conv1 of the 56x56 stage, r03 x1, but its statistics
   // epilogue sums each 64-row group in another order: the forward would no longer be bit-identical to bn_apply + conv2d_fwd_stats.  Not taken.)
-  const bool wide = d->K >= 128;
-  const int sp = sp_fwd_mode(d);
-  const unsigned grid = wide ? (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128)) : (unsigned)((sp ? cdiv(p.M, 128) : cdiv(p.M, 256)) * cdiv(d->K, 64));
-#define FWDS(BM_, BN_, WM_, WN_, SP_) hipLaunchKernelGGL((conv_fwd_k<BM_, BN_, WM_, WN_, 32, true, false, true, false, false, 0, 2, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, (const float*)nullptr, (const float*)nullptr, y)
-  if (sp == 2) { if (wide) FWDS(128, 128, 2, 2, 2); else FWDS(128, 64, 2, 2, 2); }
-  else if (sp) { if (wide) FWDS(128, 128, 2, 2, 1); else FWDS(128, 64, 2, 2, 1); }
-  else    { if (wide) FWDS(128, 128, 2, 2, 0); else FWDS(256, 64, 4, 1, 0); }
-#undef FWDS
+  fwd_launch<32, 0, true, 0, false, 0, 2>({fwd_tile(d), 1, s, &p, x, w, nullptr, nullptr, y});
   SSV_CHECK_LAUNCH("ssv_conv2d_fwd_sumin_stats");
   return SSV_OK;
 }
@@ -2019,6 +2022,43 @@ extern "C" int ssv_conv2d_fwd_bnrelu_in_stats(const ssv_conv_desc* d, const floa
   return SSV_OK;
 }
 
+namespace {
+// The strided data-gradient kernel's tile, K-step and arithmetic, and its grid: x = row tiles of the largest parity class (0,0) times column tiles,
+// y = the stride^2 parity classes.  bf16 pieces on the 128 x 128 tile with whole 32-channel k-tiles only.
+struct DgradTile { int bm, bn, bk; bool sp; int64_t row_tiles; dim3 grid; };
+inline DgradTile dgrad_tile(const ssv_conv_desc* d, int groups = 0) {
+  DgradTile t;
+  const bool wide = d->C >= 128 && groups <= 1;
+  t.bm = wide ? 128 : 256;
+  t.bn = wide ? 128 : 64;
+  t.bk = d->K % 32 == 0 ? 32 : 16;
+  t.sp = wide && t.bk == 32 && sp_dgrad_ok(d);
+  const int st = d->stride;
+  t.row_tiles = cdiv64((int64_t)d->N * cdiv(d->H, st) * cdiv(d->W, st), t.bm);
+  t.grid = dim3((unsigned)(t.row_tiles * cdiv(d->C, t.bn)), (unsigned)(st * st));
+  return t;
+}
+
+// K-step 16 exists ungated only (the gated entry point requires K % 32 == 0), the GELU epilogue on the 128 x 128 fp32 K-step-32 kernel only.
+template <bool EPI, int GATE>
+inline void dgrad_launch(const DgradTile& t, hipStream_t s, const ConvKP& p, const float* dy, const float* w, const float* addend, float* dx) {
+  auto go = [&](auto BM, auto BN, auto WGM, auto WGN, auto BK, auto SP) {
+    hipLaunchKernelGGL((conv_dgrad_k<decltype(BM)::value, decltype(BN)::value, decltype(WGM)::value, decltype(WGN)::value, decltype(BK)::value, EPI, GATE, decltype(SP)::value>),
+                       t.grid, dim3(256), 0, s, p, dy, w, addend, dx);
+  };
+  if (t.bn == 128) {
+    if (t.bk == 32 && !t.sp) go(ic<128>{}, ic<128>{}, ic<2>{}, ic<2>{}, ic<32>{}, std::false_type{});
+    else if constexpr (!EPI) {
+      if (t.sp) go(ic<128>{}, ic<128>{}, ic<2>{}, ic<2>{}, ic<32>{}, std::true_type{});
+      else if constexpr (GATE == 0) go(ic<128>{}, ic<128>{}, ic<2>{}, ic<2>{}, ic<16>{}, std::false_type{});
+    }
+  } else if constexpr (!EPI) {
+    if (t.bk == 32) go(ic<256>{}, ic<64>{}, ic<4>{}, ic<1>{}, ic<32>{}, std::false_type{});
+    else if constexpr (GATE == 0) go(ic<256>{}, ic<64>{}, ic<4>{}, ic<1>{}, ic<16>{}, std::false_type{});
+  }
+}
+}  // namespace
+
 // Linear + GELU with both tensors kept (the pre-activation h for the backward, gelu(h) for the next layer): one GEMM, one
 // epilogue; and its counterpart, dgrad with the GELU derivative applied to the product before the addend.
 extern "C" int ssv_linear_gelu_fwd(const ssv_conv_desc* d, const float* x, const float* w, const float* bias, float* h, float* act, void* stream) {
@@ -2030,14 +2070,9 @@ extern "C" int ssv_linear_gelu_fwd(const ssv_conv_desc* d, const float* x, const
   ProfScope ps(SSV_PROF_CONV_FWD, s);
   ConvKP p = make_kp(d);
   p.aux_out = act;
-  const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
   // K-step 32 only: its LDS stage is what the vectorised epilogue (the one that writes the second tensor) needs
-#define FWDE(E_, SP_, OUT_) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, E_, false, 0, false, 0, 0, false, SP_>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, OUT_)
-  const int sp = sp_fwd_mode(d);
-  if (sp == 2)  { if (h) FWDE(1, 2, h); else FWDE(3, 2, act); }
-  else if (sp)  { if (h) FWDE(1, 1, h); else FWDE(3, 1, act); }
-  else          { if (h) FWDE(1, 0, h); else FWDE(3, 0, act); }
-#undef FWDE
+  if (h) fwd_launch<32, 1>({fwd_tile(d), 1, s, &p, x, w, bias, nullptr, h});
+  else   fwd_launch<32, 3>({fwd_tile(d), 1, s, &p, x, w, bias, nullptr, act});
   SSV_CHECK_LAUNCH("ssv_linear_gelu_fwd");
   return SSV_OK;
 }
@@ -2053,9 +2088,9 @@ extern "C" int ssv_conv2d_dgrad_gelu(const ssv_conv_desc* d, const float* dy, co
   ProfScope ps(SSV_PROF_CONV_DGRAD, s);
   ConvKP p = make_kp(d);
   p.aux_in = h;
-  const int64_t Mc = (int64_t)d->N * d->H * d->W;
-  const unsigned gx = (unsigned)(cdiv64(Mc, 128) * cdiv(d->C, 128));
-  hipLaunchKernelGGL((conv_dgrad_k<128, 128, 2, 2, 32, true>), dim3(gx, 1), dim3(256), 0, s, p, dy, w, addend, dx);
+  DgradTile t = dgrad_tile(d);                       // 128 x 128, K-step 32, one parity class: required above
+  t.sp = false;                                      // the GELU epilogue exists on fp32 MFMA only
+  dgrad_launch<true, 0>(t, s, p, dy, w, addend, dx);
   SSV_CHECK_LAUNCH("ssv_conv2d_dgrad_gelu");
   return SSV_OK;
 }
@@ -2074,10 +2109,7 @@ extern "C" int ssv_linear_fwd_gelugrad(const ssv_conv_desc* d, const float* dy, 
   ProfScope ps(SSV_PROF_CONV_DGRAD, s);
   ConvKP p = make_kp(d);
   p.aux_in = h;
-  const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
-  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2, false, 0, false, 0, 0, false, 1>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
+  fwd_launch<32, 2>({fwd_tile(d), 1, s, &p, dy, wt, nullptr, addend, dh});
   SSV_CHECK_LAUNCH("ssv_linear_fwd_gelugrad");
   return SSV_OK;
 }
@@ -2093,10 +2125,7 @@ extern "C" int ssv_linear_gelu_fwd_dact(const ssv_conv_desc* d, const float* x, 
   ProfScope ps(SSV_PROF_CONV_FWD, s);
   ConvKP p = make_kp(d);
   p.aux_out = act;
-  const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
-  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4, false, 0, false, 0, 0, false, 2>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
-  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4, false, 0, false, 0, 0, false, 1>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
-  else hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 4>), dim3(grid), dim3(256), 0, s, p, x, w, bias, (const float*)nullptr, dact);
+  fwd_launch<32, 4>({fwd_tile(d), 1, s, &p, x, w, bias, nullptr, dact});
   SSV_CHECK_LAUNCH("ssv_linear_gelu_fwd_dact");
   return SSV_OK;
 }
@@ -2112,10 +2141,7 @@ extern "C" int ssv_linear_fwd_mulgrad(const ssv_conv_desc* d, const float* dy, c
   ProfScope ps(SSV_PROF_CONV_FWD, s);
   ConvKP p = make_kp(d);
   p.aux_in = dact;
-  const unsigned grid = (unsigned)(cdiv(p.M, 128) * cdiv(d->K, 128));
-  if (sp_fwd_mode(d) == 2) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5, false, 0, false, 0, 0, false, 2>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else if (sp_fwd_mode(d) == 1) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5, false, 0, false, 0, 0, false, 1>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
-  else hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, 5>), dim3(grid), dim3(256), 0, s, p, dy, wt, (const float*)nullptr, addend, dh);
+  fwd_launch<32, 5>({fwd_tile(d), 1, s, &p, dy, wt, nullptr, addend, dh});
   SSV_CHECK_LAUNCH("ssv_linear_fwd_mulgrad");
   return SSV_OK;
 }
@@ -2147,20 +2173,7 @@ int dgrad_impl(const ssv_conv_desc* d, int groups, const float* dy, const float*
   ProfScope ps(SSV_PROF_CONV_DGRAD, s);
   ConvKP p = make_kp(d);
   if (groups > 1) { p.Cg = d->C / groups; p.Kg = d->K / groups; }
-  const bool bk32 = d->K % 32 == 0;
-  const int st = d->stride;
-  const int Hq = cdiv(d->H, st), Wq = cdiv(d->W, st);            // class (0,0) is the largest
-  const int64_t Mc = (int64_t)d->N * Hq * Wq;
-  if (d->C >= 128 && groups <= 1) {
-    const dim3 g((unsigned)(cdiv64(Mc, 128) * cdiv(d->C, 128)), st * st);
-    if (bk32 && sp_dgrad_ok(d)) hipLaunchKernelGGL((conv_dgrad_k<128, 128, 2, 2, 32, false, 0, true>), g, dim3(256), 0, s, p, dy, w, addend, dx);
-    else if (bk32) hipLaunchKernelGGL((conv_dgrad_k<128, 128, 2, 2, 32>), g, dim3(256), 0, s, p, dy, w, addend, dx);
-    else      hipLaunchKernelGGL((conv_dgrad_k<128, 128, 2, 2, 16>), g, dim3(256), 0, s, p, dy, w, addend, dx);
-  } else {
-    const dim3 g((unsigned)(cdiv64(Mc, 256) * cdiv(d->C, 64)), st * st);
-    if (bk32) hipLaunchKernelGGL((conv_dgrad_k<256, 64, 4, 1, 32>), g, dim3(256), 0, s, p, dy, w, addend, dx);
-    else      hipLaunchKernelGGL((conv_dgrad_k<256, 64, 4, 1, 16>), g, dim3(256), 0, s, p, dy, w, addend, dx);
-  }
+  dgrad_launch<false, 0>(dgrad_tile(d, groups), s, p, dy, w, addend, dx);
   SSV_CHECK_LAUNCH("ssv_conv2d_dgrad");
   return SSV_OK;
 }
@@ -2168,10 +2181,8 @@ int dgrad_impl(const ssv_conv_desc* d, int groups, const float* dy, const float*
 
 extern "C" int64_t ssv_conv2d_dgrad_gate_groups(const ssv_conv_desc* d) {
   if (!d || d->C <= 0 || d->stride <= 0) return 0;
-  const int st = d->stride;
-  const int64_t Mc = (int64_t)d->N * cdiv(d->H, st) * cdiv(d->W, st);
-  const int bm = d->C >= 128 ? 128 : 256;
-  return (int64_t)st * st * cdiv64(Mc, bm) * (bm / 64);
+  const DgradTile t = dgrad_tile(d);
+  return (int64_t)t.grid.y * t.row_tiles * (t.bm / 64);
 }
 
 extern "C" int ssv_conv2d_dgrad_gated(const ssv_conv_desc* d, const float* dy, const float* w, const float* addend, float* dx,
@@ -2186,20 +2197,8 @@ extern "C" int ssv_conv2d_dgrad_gated(const ssv_conv_desc* d, const float* dy, c
   ProfScope ps(SSV_PROF_CONV_DGRAD, s);
   ConvKP p = make_kp(d);
   p.gate = *gate;
-  const int st = d->stride;
-  const int64_t Mc = (int64_t)d->N * cdiv(d->H, st) * cdiv(d->W, st);
-#define DG(BM_, BN_, WM_, WN_, G_) hipLaunchKernelGGL((conv_dgrad_k<BM_, BN_, WM_, WN_, 32, false, G_>), g, dim3(256), 0, s, p, dy, w, addend, dx)
-#define DGS(G_) hipLaunchKernelGGL((conv_dgrad_k<128, 128, 2, 2, 32, false, G_, true>), g, dim3(256), 0, s, p, dy, w, addend, dx)
-  if (d->C >= 128) {
-    const dim3 g((unsigned)(cdiv64(Mc, 128) * cdiv(d->C, 128)), st * st);
-    if (sp_dgrad_ok(d)) { if (gate->mask) DGS(2); else DGS(1); }
-    else if (gate->mask) DG(128, 128, 2, 2, 2); else DG(128, 128, 2, 2, 1);
-  } else {
-    const dim3 g((unsigned)(cdiv64(Mc, 256) * cdiv(d->C, 64)), st * st);
-    if (gate->mask) DG(256, 64, 4, 1, 2); else DG(256, 64, 4, 1, 1);
-  }
-#undef DG
-#undef DGS
+  if (gate->mask) dgrad_launch<false, 2>(dgrad_tile(d), s, p, dy, w, addend, dx);
+  else            dgrad_launch<false, 1>(dgrad_tile(d), s, p, dy, w, addend, dx);
   SSV_CHECK_LAUNCH("ssv_conv2d_dgrad_gated");
   return SSV_OK;
 }
@@ -2224,6 +2223,22 @@ extern "C" int ssv_conv2d_wgrad(const ssv_conv_desc* d, const float* x, const fl
 namespace {
 int wgrad_impl(const ssv_conv_desc* d, const float* x, const float* in_scale, const float* in_shift, const float* dy, const ssv_bn_dyin* dyin,
                float* dw, int accumulate, void* ws, size_t ws_bytes, void* stream, int groups = 0, float* dbias = nullptr);
+
+// The weight-gradient kernel on a (bm, bn) tile of plan_wgrad / plan_batched_wgrad, in fp32 MFMA or bf16 pieces; the caller gives the variant in
+// conv_wgrad_k's own parameter order.  The scalar gather (VECB false) exists on 128-column tiles and fp32 MFMA only.
+struct WgradArgs { int bm, bn; bool sp; dim3 grid; hipStream_t s; const ConvKP* p; const float* x; const float* dy; float* part; int chunk, tiles; };
+template <int BK, bool VECB, int GATHER, bool XF = false, bool DYF = false, bool BIAS = false, int FLUSH = 0>
+inline void wgrad_launch(const WgradArgs& a) {
+  auto arith = [&](auto SP) {
+    auto tile = [&](auto BM, auto BN, auto WGM, auto WGN) {
+      hipLaunchKernelGGL((conv_wgrad_k<decltype(BM)::value, decltype(BN)::value, decltype(WGM)::value, decltype(WGN)::value, BK, VECB, GATHER, XF, DYF, BIAS, FLUSH, decltype(SP)::value != 0>),
+                         a.grid, dim3(256), 0, a.s, *a.p, a.x, a.dy, a.part, a.chunk, a.tiles);
+    };
+    if (!VECB || a.bn == 128) { if (a.bm == 128) tile(ic<128>{}, ic<128>{}, ic<2>{}, ic<2>{}); else tile(ic<64>{}, ic<128>{}, ic<1>{}, ic<4>{}); }
+    else if constexpr (VECB)  { if (a.bm == 128) tile(ic<128>{}, ic<64>{}, ic<2>{}, ic<2>{});  else tile(ic<64>{}, ic<64>{}, ic<2>{}, ic<2>{}); }
+  };
+  if constexpr (VECB) for_value<1, 0>(a.sp, arith); else for_value<0>(a.sp, arith);
+}
 }
 // Weight AND bias gradient of a Linear / 1x1 / stride-1 / unpadded layer in one pass over dY (nn.Linear backward: dW = dY^T X, db = column sums
 // of dY): the weight-gradient workgroups of column tile 0 sum the dY rows they stage anyway.  C % 4 == 0, K % 4 == 0.
@@ -2292,50 +2307,13 @@ int wgrad_impl(const ssv_conv_desc* d, const float* x, const float* in_scale, co
   // gather mode of the X operand (see conv_wgrad_k): LIN, S1 (needs one carry per K-step: BK/Wo + 1 <= Ho, Ho == H, Wo == W) or generic
   const bool s1ok = d->stride == 1 && d->Ho == d->H && d->Wo == d->W && 32 / d->Wo + 1 <= d->Ho;
   const int gather = (d->R == 1 && d->S == 1 && d->pad == 0 && d->stride == 1) ? 1 : (s1ok ? 2 : 0);
-  const bool sp = sp_wgrad_ok(d, groups);
-#define WG_LAUNCH_(BM_, BN_, WM_, WN_, B_, V_, G_, X_, SP_) \
-  hipLaunchKernelGGL((conv_wgrad_k<BM_, BN_, WM_, WN_, B_, V_, G_, X_, false, false, 0, SP_>), grid, dim3(256), 0, s, p, x, dy, part, wp.chunk, tiles)
-#define WG_LAUNCH(BM_, BN_, WM_, WN_, B_, V_, G_, X_) WG_LAUNCH_(BM_, BN_, WM_, WN_, B_, V_, G_, X_, false)
-#define WG_LAUNCH_A(BM_, BN_, WM_, WN_, G_, X_) do { if (sp) WG_LAUNCH_(BM_, BN_, WM_, WN_, 32, true, G_, X_, true); else WG_LAUNCH_(BM_, BN_, WM_, WN_, 32, true, G_, X_, false); } while (0)
-#define WG_DYIN_(BM_, BN_, WM_, WN_, X_, SP_) \
-  hipLaunchKernelGGL((conv_wgrad_k<BM_, BN_, WM_, WN_, 32, true, 1, X_, true, false, 0, SP_>), grid, dim3(256), 0, s, p, x, dy, part, wp.chunk, tiles)
-#define WG_DYIN(BM_, BN_, WM_, WN_, X_) do { if (sp) WG_DYIN_(BM_, BN_, WM_, WN_, X_, true); else WG_DYIN_(BM_, BN_, WM_, WN_, X_, false); } while (0)
-#define WG_GATHER(BM_, BN_, WM_, WN_, X_) \
-  do { if (gather == 1) WG_LAUNCH_A(BM_, BN_, WM_, WN_, 1, X_); else if (gather == 2) WG_LAUNCH_A(BM_, BN_, WM_, WN_, 2, X_); \
-       else WG_LAUNCH_A(BM_, BN_, WM_, WN_, 0, X_); } while (0)
-#define WG_BIAS_(BM_, BN_, WM_, WN_, SP_) \
-  hipLaunchKernelGGL((conv_wgrad_k<BM_, BN_, WM_, WN_, 32, true, 1, false, false, true, 0, SP_>), grid, dim3(256), 0, s, p, x, dy, part, wp.chunk, tiles)
-#define WG_BIAS(BM_, BN_, WM_, WN_) do { if (sp) WG_BIAS_(BM_, BN_, WM_, WN_, true); else WG_BIAS_(BM_, BN_, WM_, WN_, false); } while (0)
-  if (dbias) {                                     // preconditions checked by ssv_conv2d_wgrad_bias: LIN gather, float4 columns
-    if (wp.bm == 128) { if (wp.bn == 64) WG_BIAS(128, 64, 2, 2); else WG_BIAS(128, 128, 2, 2); }
-    else              { if (wp.bn == 64) WG_BIAS(64, 64, 2, 2);  else WG_BIAS(64, 128, 1, 4); }
-  } else if (dyin) {                                      // preconditions checked by ssv_conv2d_wgrad_dyin: LIN gather, float4 columns
-    if (wp.bm == 128) {
-      if (wp.bn == 64) { if (xf) WG_DYIN(128, 64, 2, 2, true); else WG_DYIN(128, 64, 2, 2, false); }
-      else             { if (xf) WG_DYIN(128, 128, 2, 2, true); else WG_DYIN(128, 128, 2, 2, false); }
-    } else {
-      if (wp.bn == 64) { if (xf) WG_DYIN(64, 64, 2, 2, true); else WG_DYIN(64, 64, 2, 2, false); }
-      else             { if (xf) WG_DYIN(64, 128, 1, 4, true); else WG_DYIN(64, 128, 1, 4, false); }
-    }
-  } else if (!vecb) {
-    if (wp.bm == 128) WG_LAUNCH(128, 128, 2, 2, GBK, false, 0, false);
-    else              WG_LAUNCH(64, 128, 1, 4, GBK, false, 0, false);
-  } else if (wp.bn == 64) {                       // RSC <= 64 (and C % 4 == 0): 64-wide column tile
-    if (wp.bm == 128) { if (xf) WG_GATHER(128, 64, 2, 2, true); else WG_GATHER(128, 64, 2, 2, false); }
-    else              { if (xf) WG_GATHER(64, 64, 2, 2, true); else WG_GATHER(64, 64, 2, 2, false); }
-  } else if (wp.bm == 128) {
-    if (xf) WG_GATHER(128, 128, 2, 2, true); else WG_GATHER(128, 128, 2, 2, false);
-  } else {
-    if (xf) WG_GATHER(64, 128, 1, 4, true); else WG_GATHER(64, 128, 1, 4, false);
-  }
-#undef WG_GATHER
-#undef WG_DYIN
-#undef WG_DYIN_
-#undef WG_BIAS
-#undef WG_BIAS_
-#undef WG_LAUNCH
-#undef WG_LAUNCH_A
-#undef WG_LAUNCH_
+  const bool sp = sp_wgrad_ok(d);
+  // the scalar gather (C % 4 != 0) has 128-column tiles and fp32 MFMA only: where the plan says 64 columns (R S C <= 64) either width is ONE column tile
+  const WgradArgs a = {wp.bm, vecb ? wp.bn : 128, sp, grid, s, &p, x, dy, part, wp.chunk, tiles};
+  if (dbias)       wgrad_launch<32, true, 1, false, false, true>(a);                // preconditions checked by ssv_conv2d_wgrad_bias: LIN gather, float4 columns
+  else if (dyin)   for_value<1, 0>(xf, [&](auto X) { wgrad_launch<32, true, 1, decltype(X)::value != 0, true>(a); });      // ... by ssv_conv2d_wgrad_dyin: LIN gather, float4 columns
+  else if (!vecb)  wgrad_launch<GBK, false, 0>(a);
+  else for_value<1, 2, 0>(gather, [&](auto G) { for_value<1, 0>(xf, [&](auto X) { wgrad_launch<32, true, decltype(G)::value, decltype(X)::value != 0>(a); }); });
   SSV_CHECK_LAUNCH("ssv_conv2d_wgrad(partial)");
   const int64_t n = (int64_t)d->K * p.RSC;
   hipLaunchKernelGGL(wgrad_reduce_k, dim3((unsigned)cdiv64(n, 64)), dim3(256), 0, s, (const float*)part, wp.nsplit, n, dw, accumulate);
@@ -2677,14 +2655,11 @@ extern "C" int ssv_gemm_batched(int32_t batch, int64_t rows, int32_t C, int32_t 
   ProfScope ps(SSV_PROF_CONV_FWD, s);
   ConvKP p = make_kp(&d);
   p.bs_a = rows * C; p.bs_b = (long long)K * C; p.bs_o = rows * K;
-  const bool wide = K >= 128;
   // (Tried: ONE resident round of workgroups, each walking a contiguous run of (tile, batch) units as one continuous k-stream, so that a unit's
   // epilogue runs under the next unit's first loads - the products alone got 10-12 % faster (0.533 -> 0.478 ms at 14x14 x 256), the two-stream
   // training step did not move (231.8 vs 231.7 ms, r03 e2): the other view's kernels already fill those bubbles, and a persistent grid shuts
   // them out.  Not kept.)
-  const dim3 grid((unsigned)(wide ? cdiv(p.M, 128) * cdiv(K, 128) : cdiv(p.M, 256) * cdiv(K, 64)), (unsigned)batch);
-  if (wide) hipLaunchKernelGGL((conv_fwd_k<128, 128, 2, 2, 32, true, false, false, false, false>), grid, dim3(256), 0, s, p, a, w, (const float*)nullptr, (const float*)nullptr, y);
-  else      hipLaunchKernelGGL((conv_fwd_k<256, 64, 4, 1, 32, true, false, false, false, false>), grid, dim3(256), 0, s, p, a, w, (const float*)nullptr, (const float*)nullptr, y);
+  fwd_launch<32, 0, false, 0, false, 0, 0, false, ARITH_F32>({fwd_tile(&d), (unsigned)batch, s, &p, a, w, nullptr, nullptr, y});     // d.arithmetic == SSV_ARITH_F32_MFMA
   SSV_CHECK_LAUNCH("ssv_gemm_batched");
   return SSV_OK;
 }
@@ -2706,13 +2681,9 @@ extern "C" int ssv_gemm_batched_split(int32_t batch, int64_t rows, int32_t C, in
   p.bs_a = rows * C; p.bs_b = (long long)K * C; p.bs_o = rows * K;
   p.wp_stride = (long long)batch * K * C;
   SSV_REQUIRE(p.wp_stride * 6 < (1ll << 31), "ssv_gemm_batched_split: weight planes of 2 GiB or more");
-  const bool wide = K >= 128;
-  const dim3 grid((unsigned)(cdiv(p.M, 128) * cdiv(K, wide ? 128 : 64)), (unsigned)batch);
-  const float* w = nullptr;
-#define BSP(BN_, SP_) hipLaunchKernelGGL((conv_fwd_k<128, BN_, 2, 2, 32, true, false, false, false, false, 0, 0, false, SP_>), grid, dim3(256), 0, s, p, a, w, bias, addend, y)
-  if (C > SP_DUAL_FROM) { if (wide) BSP(128, 2); else BSP(64, 2); }
-  else                  { if (wide) BSP(128, 1); else BSP(64, 1); }
-#undef BSP
+  const FwdTile t = fwd_tile(&d);                   // two accumulators exactly when C > SP_DUAL_FROM
+  SSV_REQUIRE(t.sp != 0, "ssv_gemm_batched_split: no bf16-piece variant for this product");      // refuses, never falls back to fp32 MFMA
+  fwd_launch<32, 0, false, 0, false, 0, 0, false, ARITH_SPLIT>({t, (unsigned)batch, s, &p, a, nullptr, bias, addend, y});
   SSV_CHECK_LAUNCH("ssv_gemm_batched_split");
   return SSV_OK;
 }
@@ -2740,18 +2711,8 @@ BatchedWgradPlan plan_batched_wgrad(int batch, int64_t rows, int C, int K, int m
   w.bm = K >= 128 ? 128 : 64;
   w.bn = C <= 64 ? 64 : 128;
   w.tiles = cdiv(K, w.bm) * cdiv(C, w.bn);
-  const int slots = w.bm == 128 ? 768 : 1024;                 // one resident round over ALL batches (round down: see plan_wgrad)
-  int64_t ns = slots / ((int64_t)w.tiles * batch);
-  const int64_t max_by_rows = cdiv64(rows, 256);
-  if (ns > max_by_rows) ns = max_by_rows;
-  if (ns < 1) ns = 1;
-  int64_t chunk = cdiv64(cdiv64(rows, ns), 32) * 32;
-  if (max_chunk > 0 && chunk > max_chunk) {                   // blocked accumulation: no fp32 chain longer than max_chunk rows; equal chunks
-    const int64_t nb = cdiv64(rows, (int64_t)max_chunk);
-    chunk = cdiv64(cdiv64(rows, nb), 32) * 32;
-  }
-  w.chunk = (int)chunk;
-  w.nsplit = (int)cdiv64(rows, chunk);
+  const RowSplit rs = wgrad_row_split(w.bm, (int64_t)w.tiles * batch, rows, max_chunk);      // one resident round over ALL batches
+  w.chunk = rs.chunk; w.nsplit = rs.nsplit;
   return w;
 }
 }  // namespace
@@ -2787,17 +2748,9 @@ static int gemm_batched_wgrad(int32_t batch, int64_t rows, int32_t C, int32_t K,
   float* part = (float*)ws;
   SSV_REQUIRE((int64_t)wp.tiles * wp.nsplit < (1ll << 31), "%s: too many workgroups", who);
   const dim3 grid((unsigned)(wp.tiles * wp.nsplit), (unsigned)batch);
-#define BWG_(BM_, BN_, WM_, WN_, FL_, SP_) hipLaunchKernelGGL((conv_wgrad_k<BM_, BN_, WM_, WN_, 32, true, 1, false, false, false, FL_, SP_>), grid, dim3(256), 0, s, p, x, dy, part, wp.chunk, wp.tiles)
-#define BWG(BM_, BN_, WM_, WN_, FL_) do { if (sp) BWG_(BM_, BN_, WM_, WN_, FL_, true); else BWG_(BM_, BN_, WM_, WN_, FL_, false); } while (0)
-  if (flush_rows > 0) {                       // two-level accumulation: blocks of 4 k-tiles = 128 rows
-    if (wp.bm == 128) { if (wp.bn == 64) BWG(128, 64, 2, 2, 4); else BWG(128, 128, 2, 2, 4); }
-    else              { if (wp.bn == 64) BWG(64, 64, 2, 2, 4); else BWG(64, 128, 1, 4, 4); }
-  } else {
-    if (wp.bm == 128) { if (wp.bn == 64) BWG(128, 64, 2, 2, 0); else BWG(128, 128, 2, 2, 0); }
-    else              { if (wp.bn == 64) BWG(64, 64, 2, 2, 0); else BWG(64, 128, 1, 4, 0); }
-  }
-#undef BWG
-#undef BWG_
+  const WgradArgs a = {wp.bm, wp.bn, sp, grid, s, &p, x, dy, part, wp.chunk, wp.tiles};
+  if (flush_rows > 0) wgrad_launch<32, true, 1, false, false, false, 4>(a);      // two-level accumulation: blocks of 4 k-tiles = 128 rows
+  else                wgrad_launch<32, true, 1>(a);
   SSV_CHECK_LAUNCH("ssv_gemm_batched_wgrad(partial)");
   const int64_t n = (int64_t)K * C;
   if (max_chunk > 0 || flush_rows > 0) hipLaunchKernelGGL(wgrad_reduce64_k, dim3((unsigned)cdiv64(n, 64), (unsigned)batch), dim3(256), 0, s, (const float*)part, wp.nsplit, n, dw, 0);

@@ -17,49 +17,49 @@ ops.arithmetic("f32") and once under ops.arithmetic("bf16x3"), and each run is h
   (f) the bitwise identities the code states: fused forward variants == the plain forward on the materialised operand, the closing-activation
       forward == ssv_bn_apply + ssv_conv2d_fwd_stats, gated outputs == the masked plain output.
 
-Branches (label, forms, where conv_mfma.hip selects it) - test_case_table_covers_every_documented_branch keeps CASES honest:
+Branches (label, forms, the function of conv_mfma.hip that selects it) - test_case_table_covers_every_documented_branch keeps CASES honest:
 
-  fwd.wide                 f32 sp1 sp2   conv_mfma.hip:2105  ssv_conv2d_fwd, float4 path, 128x128 tile (K >= 128)
-  fwd.narrow               f32 sp1 sp2   conv_mfma.hip:2105  ssv_conv2d_fwd, float4 path, 256x64 (f32) / 128x64 (bf16x3) tile
-  fwd.bk16                 f32           conv_mfma.hip:2107  ssv_conv2d_fwd, C % 16 == 0 but not % 32
-  fwd.generic              f32           conv_mfma.hip:2110  ssv_conv2d_fwd, C % 16 != 0 (scalar gather)
-  fwd.k_unaligned          f32           conv_mfma.hip:2105  ssv_conv2d_fwd, K % 4 != 0 (scalar epilogue)
-  fwd.stats                f32 sp1 sp2   conv_mfma.hip:2094  ssv_conv2d_fwd_stats
-  fwd.xf                   f32 sp1 sp2   conv_mfma.hip:2095  ssv_conv2d_fwd_bnrelu_in_stats, fused input only
-  fwd.xf_stats             f32 sp1 sp2   conv_mfma.hip:2093  ssv_conv2d_fwd_bnrelu_in_stats, fused input + statistics
-  fwd.gate_affine          f32 sp1 sp2   conv_mfma.hip:2070  ssv_conv2d_fwd_gated, scale / shift gate
-  fwd.gate_mask            f32 sp1 sp2   conv_mfma.hip:2070  ssv_conv2d_fwd_gated, byte-mask gate
-  fwd.gate_x2              f32 sp1 sp2   conv_mfma.hip:2070  ssv_conv2d_fwd_gated, byte mask + second target x2
-  fwd.gate_s2add           f32 sp1 sp2   conv_mfma.hip:2067  ssv_conv2d_fwd_gated_s2add (mask, mask + x2)
-  fwd.dyin                 f32 sp1 sp2   conv_mfma.hip:2245  ssv_conv2d_fwd_dyin, no gate
-  fwd.dyin_gate            f32 sp1 sp2   conv_mfma.hip:2245  ssv_conv2d_fwd_dyin with affine / mask / x2 gates
-  fwd.dyin_s2add           f32 sp1 sp2   conv_mfma.hip:2242  ssv_conv2d_fwd_dyin_s2add
-  fwd.sumin                f32 sp1 sp2   conv_mfma.hip:2291  ssv_conv2d_fwd_sumin_stats (+- rscale / rshift, +- mask_out)
-  lin.gelu                 f32 sp1 sp2   conv_mfma.hip:2348  ssv_linear_gelu_fwd (h kept / act only)
-  lin.gelu_dact            f32 sp1 sp2   conv_mfma.hip:2413  ssv_linear_gelu_fwd_dact
-  lin.mulgrad              f32 sp1 sp2   conv_mfma.hip:2432  ssv_linear_fwd_mulgrad
-  lin.gelugrad             f32 sp1 sp2   conv_mfma.hip:2394  ssv_linear_fwd_gelugrad
-  dgrad.gelu               f32           conv_mfma.hip:2369  ssv_conv2d_dgrad_gelu (strided kernel, fp32 only)
-  dgrad.s1_as_fwd          f32 sp1 sp2   ops.py conv2d_dgrad  stride 1: forward kernel on the transposed filter (conv_mfma.hip:2105)
-  dgrad.wide_bk32          f32 sp1       conv_mfma.hip:2472  ssv_conv2d_dgrad, C >= 128, K % 32 == 0
-  dgrad.wide_bk16          f32           conv_mfma.hip:2474  ssv_conv2d_dgrad, C >= 128, K % 16 only
-  dgrad.narrow_bk32        f32           conv_mfma.hip:2477  ssv_conv2d_dgrad, C < 128, K % 32 == 0
-  dgrad.narrow_bk16        f32           conv_mfma.hip:2478  ssv_conv2d_dgrad, C < 128, K % 16 only
-  dgrad.gate_wide          f32 sp1       conv_mfma.hip:2511  ssv_conv2d_dgrad_gated, C >= 128 (affine, mask)
-  dgrad.gate_narrow        f32           conv_mfma.hip:2515  ssv_conv2d_dgrad_gated, C < 128 (affine, mask)
-  wgrad.lin                f32 sp1       conv_mfma.hip:2610  ssv_conv2d_wgrad, LIN gather (1x1 / s1 / p0)
-  wgrad.s1                 f32 sp1       conv_mfma.hip:2610  ssv_conv2d_wgrad, S1 gather (stride 1, 32 / Wo + 1 <= Ho)
-  wgrad.generic            f32 sp1       conv_mfma.hip:2610  ssv_conv2d_wgrad, generic gather (strided, tiny maps)
-  wgrad.gbk                f32           conv_mfma.hip:2637  ssv_conv2d_wgrad, C % 4 != 0
-  wgrad.bm128_bn64         f32 sp1       conv_mfma.hip:2640  128-row tile, 64-column tile (R*S*C <= 64)
-  wgrad.bm64_bn64          f32 sp1       conv_mfma.hip:2640  64-row tile, 64-column tile
-  wgrad.bm128_bn128        f32 sp1       conv_mfma.hip:2643  128 x 128 tile
-  wgrad.bm64_bn128         f32 sp1       conv_mfma.hip:2645  64 x 128 tile
-  wgrad.nsplit_ragged      f32 sp1       conv_mfma.hip:1987  plan_wgrad: several row chunks, the last one short
-  wgrad.accumulate         f32 sp1       conv_mfma.hip:2657  dw += on a nonzero prior
-  wgrad.xf                 f32 sp1       conv_mfma.hip:2640  ssv_conv2d_wgrad_bnrelu_in (LIN, S1, generic)
-  wgrad.dyin               f32 sp1       conv_mfma.hip:2630  ssv_conv2d_wgrad_dyin (+- in_affine)
-  wgrad.bias               f32 sp1       conv_mfma.hip:2626  ssv_conv2d_wgrad_bias
+  fwd.wide                 f32 sp1 sp2   conv_mfma.hip:fwd_tile  ssv_conv2d_fwd, float4 path, 128x128 tile (K >= 128)
+  fwd.narrow               f32 sp1 sp2   conv_mfma.hip:fwd_tile  ssv_conv2d_fwd, float4 path, 256x64 (f32) / 128x64 (bf16x3) tile
+  fwd.bk16                 f32           conv_mfma.hip:launch_fwd  ssv_conv2d_fwd, C % 16 == 0 but not % 32
+  fwd.generic              f32           conv_mfma.hip:launch_fwd  ssv_conv2d_fwd, C % 16 != 0 (scalar gather)
+  fwd.k_unaligned          f32           conv_mfma.hip:launch_fwd  ssv_conv2d_fwd, K % 4 != 0 (scalar epilogue)
+  fwd.stats                f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_stats
+  fwd.xf                   f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_bnrelu_in_stats, fused input only
+  fwd.xf_stats             f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_bnrelu_in_stats, fused input + statistics
+  fwd.gate_affine          f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_gated, scale / shift gate
+  fwd.gate_mask            f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_gated, byte-mask gate
+  fwd.gate_x2              f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_gated, byte mask + second target x2
+  fwd.gate_s2add           f32 sp1 sp2   conv_mfma.hip:launch_fwd  ssv_conv2d_fwd_gated_s2add (mask, mask + x2)
+  fwd.dyin                 f32 sp1 sp2   conv_mfma.hip:fwd_dyin_impl  ssv_conv2d_fwd_dyin, no gate
+  fwd.dyin_gate            f32 sp1 sp2   conv_mfma.hip:fwd_dyin_impl  ssv_conv2d_fwd_dyin with affine / mask / x2 gates
+  fwd.dyin_s2add           f32 sp1 sp2   conv_mfma.hip:fwd_dyin_impl  ssv_conv2d_fwd_dyin_s2add
+  fwd.sumin                f32 sp1 sp2   conv_mfma.hip:ssv_conv2d_fwd_sumin_stats  ssv_conv2d_fwd_sumin_stats (+- rscale / rshift, +- mask_out)
+  lin.gelu                 f32 sp1 sp2   conv_mfma.hip:ssv_linear_gelu_fwd  ssv_linear_gelu_fwd (h kept / act only)
+  lin.gelu_dact            f32 sp1 sp2   conv_mfma.hip:ssv_linear_gelu_fwd_dact  ssv_linear_gelu_fwd_dact
+  lin.mulgrad              f32 sp1 sp2   conv_mfma.hip:ssv_linear_fwd_mulgrad  ssv_linear_fwd_mulgrad
+  lin.gelugrad             f32 sp1 sp2   conv_mfma.hip:ssv_linear_fwd_gelugrad  ssv_linear_fwd_gelugrad
+  dgrad.gelu               f32           conv_mfma.hip:ssv_conv2d_dgrad_gelu  ssv_conv2d_dgrad_gelu (strided kernel, fp32 only)
+  dgrad.s1_as_fwd          f32 sp1 sp2   ops.py conv2d_dgrad  stride 1: forward kernel on the transposed filter (conv_mfma.hip:fwd_tile)
+  dgrad.wide_bk32          f32 sp1       conv_mfma.hip:dgrad_tile  ssv_conv2d_dgrad, C >= 128, K % 32 == 0
+  dgrad.wide_bk16          f32           conv_mfma.hip:dgrad_tile  ssv_conv2d_dgrad, C >= 128, K % 16 only
+  dgrad.narrow_bk32        f32           conv_mfma.hip:dgrad_tile  ssv_conv2d_dgrad, C < 128, K % 32 == 0
+  dgrad.narrow_bk16        f32           conv_mfma.hip:dgrad_tile  ssv_conv2d_dgrad, C < 128, K % 16 only
+  dgrad.gate_wide          f32 sp1       conv_mfma.hip:dgrad_tile  ssv_conv2d_dgrad_gated, C >= 128 (affine, mask)
+  dgrad.gate_narrow        f32           conv_mfma.hip:dgrad_tile  ssv_conv2d_dgrad_gated, C < 128 (affine, mask)
+  wgrad.lin                f32 sp1       conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad, LIN gather (1x1 / s1 / p0)
+  wgrad.s1                 f32 sp1       conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad, S1 gather (stride 1, 32 / Wo + 1 <= Ho)
+  wgrad.generic            f32 sp1       conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad, generic gather (strided, tiny maps)
+  wgrad.gbk                f32           conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad, C % 4 != 0
+  wgrad.bm128_bn64         f32 sp1       conv_mfma.hip:plan_wgrad  128-row tile, 64-column tile (R*S*C <= 64)
+  wgrad.bm64_bn64          f32 sp1       conv_mfma.hip:plan_wgrad  64-row tile, 64-column tile
+  wgrad.bm128_bn128        f32 sp1       conv_mfma.hip:plan_wgrad  128 x 128 tile
+  wgrad.bm64_bn128         f32 sp1       conv_mfma.hip:plan_wgrad  64 x 128 tile
+  wgrad.nsplit_ragged      f32 sp1       conv_mfma.hip:wgrad_row_split  plan_wgrad: several row chunks, the last one short
+  wgrad.accumulate         f32 sp1       conv_mfma.hip:wgrad_impl  dw += on a nonzero prior
+  wgrad.xf                 f32 sp1       conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad_bnrelu_in (LIN, S1, generic)
+  wgrad.dyin               f32 sp1       conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad_dyin (+- in_affine)
+  wgrad.bias               f32 sp1       conv_mfma.hip:wgrad_impl  ssv_conv2d_wgrad_bias
 """
 import ctypes as C
 import json
@@ -194,10 +194,22 @@ def documented_branches():
     """{(label, form)} from the module docstring's branch list."""
     out = set()
     for line in __doc__.splitlines():
-        m = re.match(r"^  ([a-z0-9_]+\.[a-z0-9_]+)\s+((?:(?:f32|sp1|sp2)\s+)+)(?:conv_mfma\.hip:\d+|ops\.py)", line)
+        m = re.match(r"^  ([a-z0-9_]+\.[a-z0-9_]+)\s+((?:(?:f32|sp1|sp2)\s+)+)(?:conv_mfma\.hip:[A-Za-z_]\w*|ops\.py)", line)
         if m:
             out |= {(m.group(1), f) for f in m.group(2).split()}
     return out
+
+
+def defines(src, name):
+    """Does the C++ text src hold a DEFINITION of function `name`: a declarator starting a line whose parameter list is followed by a body, not a `;`?"""
+    for m in re.finditer(r"^[A-Za-z][^\n;{}()]*\b%s\(" % re.escape(name), src, re.M):
+        depth, i = 1, m.end()
+        while depth and i < len(src):
+            depth += {"(": 1, ")": -1}.get(src[i], 0)
+            i += 1
+        if re.match(r"\s*\{", src[i:]):
+            return True
+    return False
 
 
 def covered_branches():
@@ -219,11 +231,11 @@ def test_case_table_covers_every_documented_branch():
     labels = {b for b, _ in doc}
     stray = {b for c in CASES for b in c.branches} - labels
     assert not stray, f"cases name undocumented branches: {sorted(stray)}"
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "self-supervised-vision_amd", "csrc", "conv_mfma.hip")).read().splitlines()
-    for line in __doc__.splitlines():
-        m = re.search(r"conv_mfma\.hip:(\d+)", line)
-        if m:
-            assert int(m.group(1)) <= len(src)
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "self-supervised-vision_amd", "csrc", "conv_mfma.hip")).read()
+    named = set(re.findall(r"conv_mfma\.hip:([A-Za-z_]\w*)", __doc__))
+    assert len(named) >= 10
+    for name in sorted(named):
+        assert defines(src, name), f"the docstring names conv_mfma.hip:{name}, which the source does not define"
     for c in CASES:
         n, h, w, ch, k, r, s, pad = c.geom
         if c.entry in FWD_KERNEL and c.form != "f32":

@@ -97,10 +97,12 @@ def test_all_53_layer_shapes_x_3_products_no_worse_than_fp32_mfma(dev, shape):
         assert esp < 2e-6, (what, esp)
 
 
-@pytest.mark.parametrize("nb,t,c,k", [(36, 1813, 128, 128), (16, 520, 256, 256), (36, 100, 512, 512), (4, 333, 64, 192), (2, 129, 1024, 132), (3, 700, 96, 64)])
+@pytest.mark.parametrize("nb,t,c,k", [(36, 1813, 128, 128), (16, 520, 256, 256), (36, 100, 512, 512), (4, 333, 64, 192), (2, 129, 1024, 132), (3, 700, 96, 64),
+                                       (2, 130, 1184, 132), (2, 130, 1184, 64), (2, 130, 64, 64)])
 def test_batched_products_ragged_shapes_bias_and_addend(dev, nb, t, c, k):
     """ssv_gemm_batched_split / ssv_gemm_batched_wgrad_split against fp64 and against the fp32-MFMA kernels: ragged row counts, channel counts that are no multiple of a
-    tile (192, 132), a 64-wide product (the 256 x 64 tile), contractions of 64 ... 1,024; then the plain 1x1 / Linear epilogue (+ bias + addend, in place)."""
+    tile (192, 132), a 64-wide product (the 256 x 64 tile), contractions of 64 ... 1,024 and of 1,184 (beyond 1,152: two accumulators, on the 128- and the 64-column
+    tile), the 64 x 64 weight-gradient tile (64 -> 64); then the plain 1x1 / Linear epilogue (+ bias + addend, in place)."""
     from ssv_amd import _lib, ops
     g = torch.Generator(device=dev).manual_seed(11)
     a = torch.randn(nb, t, c, device=dev, generator=g).clamp_min_(-0.5)
@@ -136,6 +138,33 @@ def test_batched_products_ragged_shapes_bias_and_addend(dev, nb, t, c, k):
     _lib.call("ssv_gemm_batched_split", 1, t, c, k, _lib.ptr(a[0]), _lib.ptr(pl), _lib.ptr(acc), _lib.ptr(bias), _lib.ptr(acc), _lib.stream())
     torch.cuda.synchronize()
     assert _rel(acc, want) <= 1.10 * e32 + 1e-7
+
+
+@pytest.mark.parametrize("c,k", [(64, 64), (64, 128), (128, 64), (128, 128)])
+def test_flushed_batched_weight_gradient_on_every_tile(dev, c, k):
+    """ssv_gemm_batched_wgrad_blocked with flush_rows = 128 (two-level accumulation) on fp32 MFMA, once per weight-gradient tile (64 / 128 rows x 64 / 128 columns):
+    300 ragged rows in chunks of 64, against bmm in fp64.  Element-wise |got - ref| <= 16 * 2^-24 * (|dm|^T |v|) + floor, the fp32-accumulation bound of
+    tests/test_gpu_conv_forms.py (floor = 1e-30 + 1e-3 * 2^-24 * max A): blocked accumulation and the fp64 fold of the slabs can only tighten it.  The result
+    sits in a NaN-prefilled buffer with a guard behind it."""
+    from ssv_amd import ops
+    nb, t, guard = 2, 300, 1024
+    g = torch.Generator(device=dev).manual_seed(17)
+    v = torch.randn(nb, t, c, device=dev, generator=g)
+    dm = torch.randn(nb, t, k, device=dev, generator=g)
+    ref = torch.bmm(dm.double().transpose(1, 2), v.double())
+    amag = torch.bmm(dm.double().abs().transpose(1, 2), v.double().abs())
+    buf = torch.full((nb * k * c + guard,), float("nan"), device=dev)
+    du = buf[:nb * k * c].view(nb, k, c)
+    with ops.arithmetic("f32"):
+        ops._gemm_batched_wgrad(nb, t, c, k, v, dm, du, chunk=64, flush=128)
+    torch.cuda.synchronize()
+    assert torch.isfinite(du).all(), "elements of the output never written"
+    assert torch.isnan(buf[nb * k * c:]).all(), "wrote past the end of its output"
+    u = 2.0 ** -24
+    err = (du.double() - ref).abs()
+    bound = 16.0 * u * amag + (1e-30 + 1e-3 * u * float(amag.max()))
+    print(f"flushed wgrad c={c} k={k}: worst |err| / bound = {float((err / bound).max()):.3f}")
+    assert bool((err <= bound).all()), f"{int((err > bound).sum())}/{err.numel()} elements over the bound (worst |err| / bound = {float((err / bound).max()):.2f})"
 
 
 @pytest.mark.parametrize("n,h,c", [(64, 28, 128), (64, 14, 256), (128, 7, 512), (16, 56, 64)])

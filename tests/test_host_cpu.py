@@ -360,3 +360,38 @@ def test_conv_arithmetic_falls_back_to_fp32_when_the_weight_planes_pass_2_gib():
     assert arith(1, 3, 1824, 22016, 3, 1, 0) == _lib.ARITH_F32_MFMA
     # the weight gradient has no pre-split operand: its form does not depend on the weight's size
     assert arith(8, 1, 16384, 22528, 1, 1, 2) == _lib.ARITH_BF16X3
+
+
+def test_group_count_queries_follow_the_tile_rule_of_their_launch():
+    """The gated and statistics kernels write one partial per 64-row group of every row tile they launch, and the caller sizes those buffers from the
+    *_groups queries: a query that disagrees with the launch's tile is an out-of-bounds write.  The rule, restated here: the forward tile has 128 rows
+    when K >= 128 or the launch takes the bf16-piece kernels (bf16x3 requested, 16-byte-aligned planes, C % 32 == 0, K % 4 == 0), else 256; the strided
+    data gradient's has 128 rows when C >= 128, else 256, once per parity class.  The pointers are fake addresses: the queries never dereference them."""
+    import ctypes as C
+    from ssv_amd import _lib
+    lib = _lib.load()
+    cdiv = lambda a, b: -(-a // b)
+    arithmetics = (("f32", _lib.ARITH_F32_MFMA, None), ("bf16x3 aligned", _lib.ARITH_BF16X3, 1 << 20),
+                   ("bf16x3 misaligned", _lib.ARITH_BF16X3, (1 << 20) + 4), ("bf16x3 no planes", _lib.ARITH_BF16X3, None))
+    checked = set()
+    for m in (1, 127, 128, 129, 255, 256, 257, 513):
+        for k in (64, 68, 128, 132):
+            for c in (32, 48):
+                for name, arith, planes in arithmetics:
+                    d = _lib.ConvDesc(m, 1, 1, c, k, 1, 1, 1, 0, 1, 1)
+                    d.arithmetic, d.w_planes = arith, planes
+                    sp = arith == _lib.ARITH_BF16X3 and planes is not None and planes % 16 == 0 and c % 32 == 0 and k % 4 == 0
+                    bm = 128 if (k >= 128 or sp) else 256
+                    assert lib.ssv_conv2d_fwd_gate_groups(C.byref(d)) == cdiv(m, bm) * (bm // 64), (m, k, c, name)
+                    assert lib.ssv_conv2d_fwd_stats_groups(C.byref(d)) == cdiv(m, 64), (m, k, c, name)
+                    checked.add((k >= 128, sp, bm))
+    assert checked == {(True, True, 128), (True, False, 128), (False, True, 128), (False, False, 256)}
+    for stride in (1, 2, 3):
+        for c in (64, 128):
+            for h in (7, 8):
+                for n in (1, 33):
+                    ho = (h - 1) // stride + 1
+                    d = _lib.ConvDesc(n, h, h, c, 64, 1, 1, stride, 0, ho, ho)
+                    mc = n * cdiv(h, stride) * cdiv(h, stride)
+                    bm = 128 if c >= 128 else 256
+                    assert lib.ssv_conv2d_dgrad_gate_groups(C.byref(d)) == stride * stride * cdiv(mc, bm) * (bm // 64), (stride, c, h, n)
