@@ -436,7 +436,7 @@ int ssv_add(int64_t n, float* dst, const float* src, void* stream);
  * src: uint8 [nsrc][Hs][Ws][3] (PIL layout) resident in HBM; sample_ids (device int64[B], may be NULL = 0..B-1)
  * selects the rows.  params: [nviews][B][SSV_AUG_NPARAM] float32 records
  *   [0] jitter on, [1..4] op order (0 brightness 1 contrast 2 saturation 3 hue), [5..8] the four factors,
- *   [9] gray on, [10..13] crop top,left,height,width, [14] flip on
+ *   [9] gray on, [10..13] crop top,left,height,width, [14] flip on, [15] blur sigma (0 = none; only the *_blur entry points read it)
  * drawn by ssv_augment_params from Philox4x32-10 keyed (seed; sample id, view, step) with torchvision's
  * distributions, or supplied by the caller.  out: fp32 NHWC [nviews][B][Ho][Wo][3], normalised.
  * Pixel arithmetic is Pillow's, bit for bit (oracle/augment.py).  mean3/std3 are HOST pointers to 3 floats. */
@@ -453,6 +453,27 @@ int ssv_augment_views(int32_t B, int32_t nviews, int32_t Hs, int32_t Ws, int32_t
                       const uint8_t* src, const int64_t* sample_ids, const float* params,
                       const float* mean3_host, const float* std3_host, float* out,
                       void* ws, size_t ws_bytes, void* stream);
+/* The same chain with RandomApply(GaussianBlur(sigma ~ U[sigma_min, sigma_max]), p_blur) between the flip and ToTensor (reference
+ * utils/augmentations.py:10-17,114: ImageFilter.GaussianBlur on the PIL image).  Slot [15] of the record carries the drawn sigma as
+ * float32, 0 = no blur for that (view, sample).  ssv_augment_params_blur fills slots [0..14] exactly as ssv_augment_params does and draws
+ * slot [15] from a Philox stream of its own, keyed (seed; sample id, 1024 + view, step): u0 < p_blur applies, sigma = sigma_min +
+ * u1 (sigma_max - sigma_min) is drawn either way.  ssv_augment_views_blur gives records with slot [15] == 0 the bits of ssv_augment_views;
+ * the others pass once through a uint8 staging image in the workspace and are blurred with Pillow's arithmetic (BoxBlur.c: three
+ * extended box-blur passes along the rows, three along the columns, uint32 fixed point, uint8 between passes), one workgroup per
+ * (view, sample, channel) with the plane and its ping-pong partner in LDS: Ho * Wo <= SSV_BLUR_MAX_PIXELS, larger outputs are refused.
+ * ssv_blur_scalars: the box radius and the two fixed-point weights (radius, ww, fw) the blur kernel derives from each of n device
+ * float32 sigmas, as int32 [n][3] on the device; radius -1 = the box radius is 0 and the image is copied. */
+#define SSV_BLUR_MAX_PIXELS 81920     /* two uint8 planes in the 160 KiB of LDS */
+#define SSV_BLUR_MAX_SIGMA 1000.0
+int ssv_augment_params_blur(int32_t B, int32_t Hs, int32_t Ws, int32_t nviews, const ssv_aug_cfg* cfg, uint64_t seed, uint64_t step,
+                            const int64_t* sample_ids, int64_t sample0, double p_blur, double sigma_min, double sigma_max,
+                            float* params, void* stream);
+size_t ssv_augment_blur_workspace_bytes(int32_t B, int32_t nviews, int32_t Ho, int32_t Wo);
+int ssv_augment_views_blur(int32_t B, int32_t nviews, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
+                           const uint8_t* src, const int64_t* sample_ids, const float* params,
+                           const float* mean3_host, const float* std3_host, float* out,
+                           void* ws, size_t ws_bytes, void* stream);
+int ssv_blur_scalars(int64_t n, const float* sigma, int32_t* out, void* stream);
 /* CenterCrop -> ToTensor -> Normalize: the "img" entry of the batch (configs/simclr.yaml:24-29) */
 int ssv_center_view(int32_t B, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo, const uint8_t* src, const int64_t* sample_ids,
                     const float* mean3_host, const float* std3_host, float* out, void* stream);

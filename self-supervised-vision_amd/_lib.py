@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSV_HIP_LIB") or os.path.join(_HERE, "csrc", "libssv_hip.so")   # override: diagnostic builds only
 
-ABI_VERSION = 121        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
+ABI_VERSION = 122        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
 PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_fwd", "bn_bwd", "pool", "loss", "optim", "aug", "misc", "attn", "norm")
 
 
@@ -20,6 +20,7 @@ class SsvError(RuntimeError):
 
 
 ARITH_F32_MFMA, ARITH_BF16X3 = 0, 6      # ssv_conv_desc.arithmetic (include/ssv_hip.h)
+BLUR_MAX_PIXELS, BLUR_MAX_SIGMA = 81920, 1000.0      # SSV_BLUR_MAX_PIXELS, SSV_BLUR_MAX_SIGMA (include/ssv_hip.h)
 
 
 class ConvDesc(C.Structure):
@@ -149,6 +150,10 @@ SIGNATURES = {
     "ssv_augment_params": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(AugCfg), _u64, _u64, _vp, _i64, _vp, _vp]),
     "ssv_augment_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "ssv_augment_views": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f3, _f3, _vp, _vp, _sz, _vp]),
+    "ssv_augment_params_blur": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(AugCfg), _u64, _u64, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "ssv_augment_blur_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "ssv_augment_views_blur": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f3, _f3, _vp, _vp, _sz, _vp]),
+    "ssv_blur_scalars": (C.c_int, [_i64, _vp, _vp, _vp]),
     "ssv_center_view": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _f3, _f3, _vp, _vp]),
     "ssv_knn_workspace_bytes": (_sz, [_i64]),
     "ssv_knn_label_agreement": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),

@@ -1,7 +1,8 @@
 // Two-view augmentation on the GPU: uint8 source images resident in HBM -> normalised fp32 NHWC views.
 // The chain is the one configs/simclr.yaml:13-29 builds from torchvision transforms (reference
 // utils/augmentations.py:113-144, run per sample in DataLoader workers, utils/data_utils.py:68-73):
-//   RandomApply(ColorJitter, p) -> RandomGrayscale -> RandomResizedCrop(bilinear) -> HorizontalFlip -> ToTensor -> Normalize
+//   RandomApply(ColorJitter, p) -> RandomGrayscale -> RandomResizedCrop(bilinear) -> HorizontalFlip
+//     [-> RandomApply(GaussianBlur(sigma ~ U), p)] -> ToTensor -> Normalize
 // Integer/byte work, HBM- and L2-bound; no matrix cores.  The arithmetic mirrors Pillow's C kernels bit for bit
 // (Blend.c float lerp + truncation, Convert.c rgb2l / rgb2hsv / hsv2rgb, Resample.c triangle filter with 22-bit
 // fixed-point coefficients and a uint8 intermediate between the horizontal and the vertical pass); the CPU
@@ -12,6 +13,12 @@
 //                  statistic of the source image) and the two resampling coefficient tables of the crop;
 //   aug_views_k  : one thread per output pixel: <= KMAX x KMAX taps, the colour chain applied to each fetched source pixel;
 //   (aug_params_k draws the per-sample parameters from a counter-based Philox4x32-10 stream.)
+// A chain with gaussian_blur (the *_blur entry points) adds:
+//   aug_blur_params_k : slot [15] of the record, the drawn sigma (0 = no blur), from a Philox stream of its own (view key 1024 + view);
+//   aug_views_k<true> : as above, but a record with sigma > 0 leaves its resized uint8 pixels in a planar staging image instead of the output;
+//   aug_blur_k        : one workgroup per (view, sample, channel) of a blurred record: the plane is loaded into LDS once, Pillow's six extended
+//                       box-blur passes (BoxBlur.c: rows x 3, columns x 3, uint32 fixed point, uint8 between passes) ping-pong between two LDS
+//                       buffers, and the last one is normalised into the fp32 output.  No pass touches HBM.
 #include "common.h"
 
 namespace {
@@ -243,10 +250,12 @@ aug_prep_k(int B, int Hs, int Ws, int Ho, int Wo, const uint8_t* __restrict__ sr
   if (threadIdx.x == 0) cmean[vb] = need ? (int)((double)red[0] / (double)(Hs * Ws) + 0.5) : 0;
 }
 
+// BLUR: a record whose slot [15] (sigma) is > 0 writes its uint8 pixels to stage [vb][3][Ho][Wo] for aug_blur_k instead of normalising them
+template <bool BLUR>
 __global__ void __launch_bounds__(256)
 aug_views_k(int B, int Hs, int Ws, int Ho, int Wo, int nviews, const uint8_t* __restrict__ src, const int64_t* __restrict__ ids,
             const float* __restrict__ params, const int* __restrict__ cmean, const int* __restrict__ tabs,
-            float m0, float m1, float m2, float s0, float s1, float s2, float* __restrict__ out) {
+            float m0, float m1, float m2, float s0, float s1, float s2, float* __restrict__ out, uint8_t* __restrict__ stage) {
   const int64_t total = (int64_t)nviews * B * Ho * Wo;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int xo = (int)(i % Wo);
@@ -273,6 +282,12 @@ aug_views_k(int B, int Hs, int Ws, int Ho, int Wo, int nviews, const uint8_t* __
       }
       const int ky = vy[2 + ty];
       av0 += clip8i(a0 >> PRECISION_BITS) * ky; av1 += clip8i(a1 >> PRECISION_BITS) * ky; av2 += clip8i(a2 >> PRECISION_BITS) * ky;
+    }
+    if (BLUR && p[15] > 0.f) {
+      const size_t plane = (size_t)Ho * Wo;
+      uint8_t* q = stage + (size_t)vb * 3 * plane + (size_t)yo * Wo + xo;
+      q[0] = (uint8_t)clip8i(av0 >> PRECISION_BITS); q[plane] = (uint8_t)clip8i(av1 >> PRECISION_BITS); q[2 * plane] = (uint8_t)clip8i(av2 >> PRECISION_BITS);
+      continue;
     }
     float* o = out + (size_t)i * 3;          // ToTensor (/255) then Normalize, IEEE float32 ops
     o[0] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)clip8i(av0 >> PRECISION_BITS), 255.f), m0), s0);
@@ -361,6 +376,104 @@ __global__ void __launch_bounds__(256) multicrop_k(int64_t total, int Hs, int Ws
   o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
 }
 
+// ---- Gaussian blur: ImageFilter.GaussianBlur = BoxBlur.c ImagingGaussianBlur, three extended-box passes per direction ----------------
+// the blur draws of a record: a Philox stream of their own, so slots [0..14] are what aug_params_k alone gives
+constexpr uint32_t BLUR_VIEW_BASE = 1024;
+
+__global__ void aug_blur_params_k(int B, int nviews, double p_blur, double sigma_min, double sigma_max, uint64_t seed, uint64_t step,
+                                  const int64_t* __restrict__ ids, int64_t sample0, float* __restrict__ params) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nviews * B) return;
+  const int view = t / B, b = t - view * B;
+  Philox st(seed, step, (uint64_t)(ids ? ids[b] : sample0 + b), BLUR_VIEW_BASE + (uint32_t)view);
+  const double u0 = st.uniform(), u1 = st.uniform();
+  const float sigma = (float)__dadd_rn(sigma_min, __dmul_rn(u1, sigma_max - sigma_min));       // separately rounded, as Python evaluates it
+  params[(size_t)t * NPARAM + 15] = u0 < p_blur ? sigma : 0.f;
+}
+
+// _gaussian_blur_radius(sigma, 3) and the fixed-point weights of ImagingLineBoxBlur8.  The evaluation widths are C's: float, except where a
+// double constant promotes the expression.  radius < 0: the box radius is 0 and Pillow copies the image.
+struct BlurScalars { int radius; uint32_t ww, fw; };
+
+__device__ BlurScalars blur_scalars(float sigma) {
+  const float s2 = __fdiv_rn(__fmul_rn(sigma, sigma), 3.f);
+  const float L = (float)__dsqrt_rn(__dadd_rn(__dmul_rn(12.0, (double)s2), 1.0));
+  const float l = (float)floor(__dmul_rn(__dsub_rn((double)L, 1.0), 0.5));
+  float a = (float)__dmul_rn((double)__fadd_rn(__fmul_rn(2.f, l), 1.f),
+                             __dsub_rn((double)__fmul_rn(l, __fadd_rn(l, 1.f)), __dmul_rn(3.0, (double)s2)));
+  const float lp1 = __fadd_rn(l, 1.f);
+  a = __fdiv_rn(a, __fmul_rn(6.f, __fsub_rn(s2, __fmul_rn(lp1, lp1))));
+  const float fr = __fadd_rn(l, a);
+  BlurScalars sc;
+  if (fr == 0.f) { sc.radius = -1; sc.ww = 0; sc.fw = 0; return sc; }
+  if (!(fr < 8388608.f)) { sc.radius = 1 << 23; sc.ww = 0; sc.fw = 1u << 23; return sc; }     // 2 fr + 1 > 2^24: ww is 0, only the edge taps count
+  sc.radius = (int)fr;
+  sc.ww = (uint32_t)__fdiv_rn(16777216.f, __fadd_rn(__fmul_rn(fr, 2.f), 1.f));
+  sc.fw = ((1u << 24) - (uint32_t)(2 * sc.radius + 1) * sc.ww) / 2;
+  return sc;
+}
+
+__global__ void blur_scalars_k(int64_t n, const float* __restrict__ sigma, int32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const BlurScalars sc = blur_scalars(sigma[i]);
+  out[3 * i] = sc.radius; out[3 * i + 1] = (int32_t)sc.ww; out[3 * i + 2] = (int32_t)sc.fw;
+}
+
+// one output pixel of a pass: position `pos` of a line of `len` pixels `stride` bytes apart; edge pixels repeat (radius >= len included)
+__device__ __forceinline__ uint8_t blur_px(const uint8_t* __restrict__ line, int stride, int len, int pos, const BlurScalars& sc) {
+  const int r = sc.radius, last = len - 1;
+  int i0 = pos - r, i1 = pos + r;
+  uint32_t acc = 0;
+  if (i0 < 0) { acc += (uint32_t)(-i0) * line[0]; i0 = 0; }
+  if (i1 > last) { acc += (uint32_t)(i1 - last) * line[(size_t)last * stride]; i1 = last; }
+  for (int j = i0; j <= i1; ++j) acc += line[j * stride];
+  const uint32_t edge = (uint32_t)line[max(pos - r - 1, 0) * stride] + (uint32_t)line[min(pos + r + 1, last) * stride];
+  return (uint8_t)((sc.ww * acc + sc.fw * edge + (1u << 23)) >> 24);
+}
+
+// One workgroup per (view, sample, channel); the plane and its ping-pong partner live in LDS (2 x Ho x Wo bytes <= LDS_BYTES).
+// stage: uint8 [nviews * B][3][Ho][Wo] written by aug_views_k<true>; out: fp32 NHWC.  Records with sigma == 0 were finished by aug_views_k.
+template <int LDS_BYTES, int THREADS>
+__global__ void __launch_bounds__(THREADS)
+aug_blur_k(int Ho, int Wo, FastDiv divw, const float* __restrict__ params, const uint8_t* __restrict__ stage,
+           float m0, float m1, float m2, float s0, float s1, float s2, float* __restrict__ out) {
+  __shared__ __align__(16) uint8_t sm[LDS_BYTES];
+  const int vb = blockIdx.x / 3, c = blockIdx.x - vb * 3;
+  const float sigma = params[(size_t)vb * NPARAM + 15];
+  if (!(sigma > 0.f)) return;                                   // uniform over the workgroup
+  const int n = Ho * Wo;
+  int ao = 0, bo = LDS_BYTES / 2;                               // the pass reads sm + ao and writes sm + bo, then they swap
+  uint8_t* a = sm;
+  const uint8_t* src = stage + ((size_t)vb * 3 + c) * n;
+  if ((n & 15) == 0) {                                          // plane bases are then 16-byte aligned (the staging image is)
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    uint4* a4 = reinterpret_cast<uint4*>(a);
+    for (int i = threadIdx.x; i < (n >> 4); i += THREADS) a4[i] = s4[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += THREADS) a[i] = src[i];
+  }
+  __syncthreads();
+  const BlurScalars sc = blur_scalars(sigma);
+  if (sc.radius >= 0) {
+#pragma unroll 1
+    for (int pass = 0; pass < 6; ++pass) {
+      const bool rows = pass < 3;
+      for (int i = threadIdx.x; i < n; i += THREADS) {
+        const int y = (int)fdiv((uint32_t)i, divw), x = i - y * Wo;
+        sm[bo + i] = rows ? blur_px(sm + ao + y * Wo, 1, Wo, x, sc) : blur_px(sm + ao + x, Wo, Ho, y, sc);
+      }
+      __syncthreads();
+      const int t = ao; ao = bo; bo = t;
+    }
+  }
+  a = sm + ao;                                                  // six swaps: the first buffer again
+  const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), s = c == 0 ? s0 : (c == 1 ? s1 : s2);
+  float* o = out + (size_t)vb * n * 3 + c;
+  for (int i = threadIdx.x; i < n; i += THREADS) o[(size_t)i * 3] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)a[i], 255.f), m), s);
+}
+
+
 unsigned grid_for(int64_t n) {
   int64_t b = cdiv64(n, 256);
   if (b > 8192) b = 8192;
@@ -402,10 +515,87 @@ extern "C" int ssv_augment_views(int32_t B, int32_t nviews, int32_t Hs, int32_t 
   int* cmean = (int*)ws;
   int* tabs = cmean + (size_t)nviews * B;
   hipLaunchKernelGGL(aug_prep_k, dim3(nviews * B), dim3(256), 0, s, B, Hs, Ws, Ho, Wo, src, sample_ids, params, cmean, tabs);
-  hipLaunchKernelGGL(aug_views_k, dim3(grid_for((int64_t)nviews * B * Ho * Wo)), dim3(256), 0, s, B, Hs, Ws, Ho, Wo, nviews, src, sample_ids,
+  hipLaunchKernelGGL(aug_views_k<false>, dim3(grid_for((int64_t)nviews * B * Ho * Wo)), dim3(256), 0, s, B, Hs, Ws, Ho, Wo, nviews, src, sample_ids,
                      params, (const int*)cmean, (const int*)tabs, mean3_host[0], mean3_host[1], mean3_host[2],
-                     std3_host[0], std3_host[1], std3_host[2], out);
+                     std3_host[0], std3_host[1], std3_host[2], out, (uint8_t*)nullptr);
   SSV_CHECK_LAUNCH("ssv_augment_views");
+  return SSV_OK;
+}
+
+// ---- the chain with gaussian_blur ---------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t BLUR_STAGE_ALIGN = 256;
+size_t blur_stage_offset(int B, int nviews, int Ho, int Wo) {
+  const size_t base = ssv_augment_workspace_bytes(B, nviews, Ho, Wo);
+  return (base + BLUR_STAGE_ALIGN - 1) / BLUR_STAGE_ALIGN * BLUR_STAGE_ALIGN;
+}
+
+template <int LDS_BYTES, int THREADS>
+void launch_blur(hipStream_t s, int nvb, int Ho, int Wo, const float* params, const uint8_t* stage, const float* m, const float* sd, float* out) {
+  hipLaunchKernelGGL((aug_blur_k<LDS_BYTES, THREADS>), dim3(3 * nvb), dim3(THREADS), 0, s, Ho, Wo, make_fastdiv((uint32_t)Wo), params, stage,
+                     m[0], m[1], m[2], sd[0], sd[1], sd[2], out);
+}
+}  // namespace
+
+extern "C" int ssv_augment_params_blur(int32_t B, int32_t Hs, int32_t Ws, int32_t nviews, const ssv_aug_cfg* cfg, uint64_t seed, uint64_t step,
+                                       const int64_t* sample_ids, int64_t sample0, double p_blur, double sigma_min, double sigma_max,
+                                       float* params, void* stream) {
+  SSV_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && nviews > 0 && nviews <= 16 && cfg && params, "ssv_augment_params_blur: bad arguments");
+  SSV_REQUIRE(p_blur >= 0.0 && p_blur <= 1.0, "ssv_augment_params_blur: p_blur outside [0, 1]");
+  SSV_REQUIRE(sigma_min >= 0.0 && sigma_max >= sigma_min && sigma_max <= SSV_BLUR_MAX_SIGMA,
+              "ssv_augment_params_blur: bad sigma range (0 <= sigma_min <= sigma_max <= %g)", (double)SSV_BLUR_MAX_SIGMA);
+  const int rc = ssv_augment_params(B, Hs, Ws, nviews, cfg, seed, step, sample_ids, sample0, params, stream);
+  if (rc != SSV_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(SSV_PROF_AUG, s);
+  hipLaunchKernelGGL(aug_blur_params_k, dim3(cdiv(nviews * B, 64)), dim3(64), 0, s, B, nviews, p_blur, sigma_min, sigma_max, seed, step, sample_ids,
+                     sample0, params);
+  SSV_CHECK_LAUNCH("ssv_augment_params_blur");
+  return SSV_OK;
+}
+
+extern "C" size_t ssv_augment_blur_workspace_bytes(int32_t B, int32_t nviews, int32_t Ho, int32_t Wo) {
+  if (B <= 0 || nviews <= 0 || Ho <= 0 || Wo <= 0 || (int64_t)Ho * Wo > SSV_BLUR_MAX_PIXELS) return 0;
+  return blur_stage_offset(B, nviews, Ho, Wo) + (size_t)nviews * B * 3 * (size_t)Ho * Wo;
+}
+
+extern "C" int ssv_augment_views_blur(int32_t B, int32_t nviews, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
+                                      const uint8_t* src, const int64_t* sample_ids, const float* params,
+                                      const float* mean3_host, const float* std3_host, float* out,
+                                      void* ws, size_t ws_bytes, void* stream) {
+  SSV_REQUIRE(B > 0 && nviews > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && src && params && mean3_host && std3_host && out && ws,
+              "ssv_augment_views_blur: bad arguments");
+  SSV_REQUIRE((int64_t)Hs * Ws < (1 << 24), "ssv_augment_views_blur: source image too large");
+  SSV_REQUIRE(2 * (Hs + Ho - 1) / Ho + 1 <= KMAX && 2 * (Ws + Wo - 1) / Wo + 1 <= KMAX,
+              "ssv_augment_views_blur: down-scaling factor above 3.5 needs more than %d taps", KMAX);
+  SSV_REQUIRE((int64_t)Ho * Wo <= SSV_BLUR_MAX_PIXELS,
+              "ssv_augment_views_blur: a %d x %d output plane and its ping-pong partner do not fit the 160 KiB of LDS (Ho * Wo <= %d)", Ho, Wo, SSV_BLUR_MAX_PIXELS);
+  SSV_REQUIRE((int64_t)nviews * B <= INT32_MAX / 3, "ssv_augment_views_blur: too many (view, sample) records for one launch");
+  if (ws_bytes < ssv_augment_blur_workspace_bytes(B, nviews, Ho, Wo)) SSV_FAIL(SSV_ERR_WORKSPACE, "ssv_augment_views_blur: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(SSV_PROF_AUG, s);
+  int* cmean = (int*)ws;
+  int* tabs = cmean + (size_t)nviews * B;
+  uint8_t* stage = (uint8_t*)ws + blur_stage_offset(B, nviews, Ho, Wo);
+  SSV_REQUIRE(((uintptr_t)stage & 15) == 0, "ssv_augment_views_blur: the workspace must be 16-byte aligned");
+  hipLaunchKernelGGL(aug_prep_k, dim3(nviews * B), dim3(256), 0, s, B, Hs, Ws, Ho, Wo, src, sample_ids, params, cmean, tabs);
+  hipLaunchKernelGGL(aug_views_k<true>, dim3(grid_for((int64_t)nviews * B * Ho * Wo)), dim3(256), 0, s, B, Hs, Ws, Ho, Wo, nviews, src, sample_ids,
+                     params, (const int*)cmean, (const int*)tabs, mean3_host[0], mean3_host[1], mean3_host[2],
+                     std3_host[0], std3_host[1], std3_host[2], out, stage);
+  const int plane2 = 2 * ((Ho * Wo + 15) / 16 * 16);          // both LDS buffers, each 16-byte aligned
+  if (plane2 <= 8192) launch_blur<8192, 256>(s, nviews * B, Ho, Wo, params, stage, mean3_host, std3_host, out);
+  else if (plane2 <= 32768) launch_blur<32768, 512>(s, nviews * B, Ho, Wo, params, stage, mean3_host, std3_host, out);
+  else if (plane2 <= 65536) launch_blur<65536, 1024>(s, nviews * B, Ho, Wo, params, stage, mean3_host, std3_host, out);
+  else launch_blur<163840, 1024>(s, nviews * B, Ho, Wo, params, stage, mean3_host, std3_host, out);
+  SSV_CHECK_LAUNCH("ssv_augment_views_blur");
+  return SSV_OK;
+}
+
+extern "C" int ssv_blur_scalars(int64_t n, const float* sigma, int32_t* out, void* stream) {
+  SSV_REQUIRE(n > 0 && n <= (int64_t)1 << 30 && sigma && out, "ssv_blur_scalars: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(blur_scalars_k, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, n, sigma, out);
+  SSV_CHECK_LAUNCH("ssv_blur_scalars");
   return SSV_OK;
 }
 

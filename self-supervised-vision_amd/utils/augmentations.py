@@ -5,11 +5,15 @@ torchvision Compose that runs on PIL images in DataLoader workers.  Here the sam
 transform order) is compiled into the parameters of three kernels (csrc/augment.hip) that read the uint8
 dataset resident in HBM and write the normalised fp32 views directly: no CPU work, no H2D copy per step.
 
-Supported chains (everything the shipped simclr / byol / barlow configs use):
-  train: [color_jitter(apply_prob)] [random_gray] random_resized_crop [random_flip] to_tensor normalize
+Supported chains (everything the shipped simclr / byol / barlow configs use, and the blur of the 224 x 224 recipes):
+  train: [color_jitter(apply_prob)] [random_gray] random_resized_crop [random_flip] [gaussian_blur(sigma, apply_prob)] to_tensor normalize
   test : center_crop to_tensor normalize
-Transforms registered by the reference but used by none of its configs on this path (gaussian_blur, cutout,
-rand_aug, random_crop, resize) raise NotImplementedError.
+gaussian_blur: {sigma: [lo, hi], apply_prob: p} (sigma defaults to [0.1, 2.0], a missing apply_prob means always) is Pillow's
+ImageFilter.GaussianBlur(radius = U(lo, hi)) on the uint8 image between the flip and ToTensor, bit for bit; its draws come from a Philox
+stream of their own and land in slot [15] of the parameter record, so the other slots do not depend on whether the chain has blur.  A chain
+with blur goes through the *_blur entry points (one more kernel, LDS-resident); a chain without it issues exactly the launches it always did.
+Transforms registered by the reference but used by none of its configs on this path (cutout, rand_aug, random_crop, resize), and
+gaussian_blur anywhere else in the chain, raise NotImplementedError.
 """
 import ctypes as C
 
@@ -17,7 +21,7 @@ import torch
 
 from .. import _lib
 
-_TRAIN_ORDER = ["color_jitter", "random_gray", "random_resized_crop", "random_flip", "to_tensor", "normalize"]
+_TRAIN_ORDER = ["color_jitter", "random_gray", "random_resized_crop", "random_flip", "gaussian_blur", "to_tensor", "normalize"]
 _TEST_ORDER = ["center_crop", "to_tensor", "normalize"]
 _KNOWN = {"gaussian_blur", "color_jitter", "random_gray", "random_crop", "random_resized_crop", "center_crop", "resize",
           "random_flip", "to_tensor", "normalize", "rand_aug", "cutout"}
@@ -59,6 +63,18 @@ class GpuTransform:
             float((config.get("random_gray") or {}).get("p", 0.1)) if "random_gray" in keys else 0.0,
             float((config.get("random_flip") or {}).get("p", 0.5)) if "random_flip" in keys else 0.0,
             float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1]))
+        self.blur = None                                        # (apply_prob, sigma_min, sigma_max) when the chain has gaussian_blur
+        if "gaussian_blur" in keys:
+            gb = config.get("gaussian_blur") or {}
+            sigma = gb.get("sigma", (0.1, 2.0))
+            if not isinstance(sigma, (list, tuple)) or len(sigma) != 2:
+                raise ValueError(f"gaussian_blur.sigma must be [lo, hi], got {sigma!r}")
+            lo, hi, p = float(sigma[0]), float(sigma[1]), float(gb.get("apply_prob", 1.0))
+            if not (0.0 <= lo <= hi <= _lib.BLUR_MAX_SIGMA):
+                raise ValueError(f"gaussian_blur.sigma needs 0 <= lo <= hi <= {_lib.BLUR_MAX_SIGMA}, got {sigma!r}")
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"gaussian_blur.apply_prob must lie in [0, 1], got {p!r}")
+            self.blur = (p, lo, hi)             # an output above _lib.BLUR_MAX_PIXELS is refused by the library when the chain is applied
 
     # ------------------------------------------------------------------------------------------
     def draw(self, images, idx, step, nviews=2):
@@ -66,8 +82,12 @@ class GpuTransform:
         b = idx.numel()
         _, hs, ws, _ = images.shape
         params = torch.empty((nviews, b, 16), dtype=torch.float32, device=images.device)
-        _lib.call("ssv_augment_params", b, hs, ws, nviews, C.byref(self.cfg), self.seed, int(step), _lib.ptr(idx), 0,
-                  _lib.ptr(params), _lib.stream())
+        if self.blur is None:
+            _lib.call("ssv_augment_params", b, hs, ws, nviews, C.byref(self.cfg), self.seed, int(step), _lib.ptr(idx), 0,
+                      _lib.ptr(params), _lib.stream())
+        else:
+            _lib.call("ssv_augment_params_blur", b, hs, ws, nviews, C.byref(self.cfg), self.seed, int(step), _lib.ptr(idx), 0,
+                      self.blur[0], self.blur[1], self.blur[2], _lib.ptr(params), _lib.stream())
         return params
 
     def apply(self, images, idx, params):
@@ -79,8 +99,9 @@ class GpuTransform:
         _, hs, ws, _ = images.shape
         ho, wo = self.size
         out = torch.empty((v, b, ho, wo, 3), dtype=torch.float32, device=images.device)
-        ws_t = _lib.workspace.get(_lib.load().ssv_augment_workspace_bytes(b, v, ho, wo), images.device)
-        _lib.call("ssv_augment_views", b, v, hs, ws, ho, wo, _lib.ptr(images), _lib.ptr(idx), _lib.ptr(params.contiguous()),
+        blur = "_blur" if self.blur is not None else ""          # slot [15] of the records is read by the blur entry point only
+        ws_t = _lib.workspace.get(getattr(_lib.load(), f"ssv_augment{blur}_workspace_bytes")(b, v, ho, wo), images.device)
+        _lib.call(f"ssv_augment_views{blur}", b, v, hs, ws, ho, wo, _lib.ptr(images), _lib.ptr(idx), _lib.ptr(params.contiguous()),
                   self.mean, self.std, _lib.ptr(out), _lib.ptr(ws_t), ws_t.numel(), _lib.stream())
         return out.permute(0, 1, 4, 2, 3)
 
