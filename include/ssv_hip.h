@@ -492,6 +492,34 @@ size_t ssv_knn_workspace_bytes_arith(int64_t n, int32_t d, int32_t arithmetic);
 int ssv_knn_label_agreement_arith(int64_t n, int32_t d, const float* z, const int32_t* labels, int32_t k,
                                   unsigned long long* count, int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- k-means and the Hungarian-matched cluster accuracy (csrc/kmeans.hip): the metric the reference's README reports, which its code never computes - it has the
+ * matching (utils/eval_utils.py:23-35) and a faiss.Kmeans run over encoder features (models/deep_cluster.py:100-118), nothing joins them.
+ * x [n][d] and centroids [k][d] fp32, dense; 1 <= k <= min(n, SSV_KMEANS_MAX_K), d % 4 == 0 (pad with zero columns: exact), d <= SSV_KMEANS_MAX_D, n <= 2^30;
+ * anything else is refused, never clamped.
+ * ssv_kmeans_assign: labels[i] = argmax_j (x_i . c_j - 1/2 |c_j|^2), exact ties to the lowest j (bit-identical centroid rows score bit-identically, so a duplicate
+ * never wins against its first copy); dist[i] = max(0, |x_i|^2 + |c|^2 - 2 x_i . c) in fp32; counts[j] = rows labelled j; *objective = sum dist (per-row-block
+ * partials folded in fixed order: equal inputs give equal bits).  SSV_ARITH_BF16X3: the search is fused into the X C^T product on v_mfma_f32_32x32x16_bf16 - the n x k
+ * scores never reach memory, |x|^2 comes from the same pass, x is read once per block of 256 centroids.  SSV_ARITH_F32_MFMA: X C^T by row chunks through the
+ * workspace (ssv_conv2d_fwd), then one wavefront per row.
+ * prep: ssv_kmeans_prep_bytes(d, k) bytes the caller owns - 1/2 |c|^2 and the centroids' three bf16 planes in the fused kernel's operand order.  prep_ready == 0: the
+ * call makes them from `centroids` first (once per call); != 0: they are what ssv_kmeans_update (or an earlier assignment of the SAME centroids) left there.
+ * ssv_kmeans_update: centroids[j] = mean of the rows labelled j, formed as onehot(labels)^T X on the weight-gradient GEMM (ssv_conv2d_wgrad: products by 1 and 0 are
+ * exact, the accumulation order is fixed, no floating-point atomics) divided by counts[j]; counts[j] <= 0 keeps centroids[j]; a label outside [0, k) belongs to no
+ * cluster.  prep (may be NULL) is re-made for the next assignment.  Workspace of either call: ssv_kmeans_workspace_bytes. */
+#define SSV_KMEANS_MAX_K 4096
+#define SSV_KMEANS_MAX_D 8192
+size_t ssv_kmeans_prep_bytes(int32_t d, int32_t k);
+size_t ssv_kmeans_workspace_bytes(int64_t n, int32_t d, int32_t k, int32_t arithmetic);
+int ssv_kmeans_assign(int64_t n, int32_t d, int32_t k, const float* x, const float* centroids, void* prep, int32_t prep_ready,
+                      int32_t* labels, float* dist, int32_t* counts, float* objective, int32_t arithmetic,
+                      void* ws, size_t ws_bytes, void* stream);
+int ssv_kmeans_update(int64_t n, int32_t d, int32_t k, const float* x, const int32_t* labels, const int32_t* counts, float* centroids, void* prep,
+                      int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
+/* votes[p][t] (int64 [pred_k][targets_k], zeroed by the call) = rows with pred == p and targets == t: the table hungarian_match counts on the host
+ * (utils/eval_utils.py:25-28).  A label outside its range is not counted and sets *flag (device int32, 0 otherwise).  1 <= n < 2^31. */
+int ssv_cluster_votes(int64_t n, const int32_t* pred, const int32_t* targets, int32_t pred_k, int32_t targets_k, int64_t* votes, int32_t* flag,
+                      void* stream);
+
 /* ==== "next" row 1 of the scope table: DINO on the reference's ViT (networks/vit.py, models/dino.py) ====================
  * Linear layers of the encoder and of the projection head are ssv_conv2d_fwd/dgrad/wgrad with H = W = R = S = 1 over
  * N = B*T token rows; what follows are the pieces that are not GEMMs.  All matrices are dense row-major fp32. */

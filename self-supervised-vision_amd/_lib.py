@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSV_HIP_LIB") or os.path.join(_HERE, "csrc", "libssv_hip.so")   # override: diagnostic builds only
 
-ABI_VERSION = 122        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
+ABI_VERSION = 123        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
 PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_fwd", "bn_bwd", "pool", "loss", "optim", "aug", "misc", "attn", "norm")
 
 
@@ -21,6 +21,7 @@ class SsvError(RuntimeError):
 
 ARITH_F32_MFMA, ARITH_BF16X3 = 0, 6      # ssv_conv_desc.arithmetic (include/ssv_hip.h)
 BLUR_MAX_PIXELS, BLUR_MAX_SIGMA = 81920, 1000.0      # SSV_BLUR_MAX_PIXELS, SSV_BLUR_MAX_SIGMA (include/ssv_hip.h)
+KMEANS_MAX_K, KMEANS_MAX_D = 4096, 8192              # SSV_KMEANS_MAX_K, SSV_KMEANS_MAX_D (include/ssv_hip.h)
 
 
 class ConvDesc(C.Structure):
@@ -159,6 +160,11 @@ SIGNATURES = {
     "ssv_knn_label_agreement": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "ssv_knn_workspace_bytes_arith": (_sz, [_i64, _i32, _i32]),
     "ssv_knn_label_agreement_arith": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _sz, _vp]),
+    "ssv_kmeans_prep_bytes": (_sz, [_i32, _i32]),
+    "ssv_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "ssv_kmeans_assign": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "ssv_kmeans_update": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "ssv_cluster_votes": (C.c_int, [_i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ssv_vit_embed_fwd": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ssv_vit_embed_bwd": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "ssv_layernorm_fwd": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),

@@ -3,7 +3,7 @@
 The reference carries one ~170-line trainer per algorithm (models/simclr.py:39-167 and its siblings); on this path the
 common part exists once and an algorithm supplies four hooks (`_build`, `_embed`, `_checkpoint_state`, `_load_state`)
 plus `train_step`.  What callers of the reference rely on is kept: ``Cls(args: dict)``; ``train()``,
-``train_step(batch) -> {"loss": float}``, ``knn_validate()``, ``build_features(split)``, ``perform_linear_eval()``,
+``train_step(batch) -> {"loss": float}``, ``knn_validate()``, ``cluster_validate()``, ``build_features(split)``, ``perform_linear_eval()``,
 ``save_checkpoint()``, ``load_checkpoint(dir)``, ``adjust_learning_rate(epoch)``; attributes ``config, output_dir, logger,
 device, optim, scheduler, loss_fn, best_metric``; the log-line formats; ``best_model.pt`` in the run directory.
 """
@@ -154,6 +154,14 @@ class TwoViewTrainer:
     @torch.no_grad()
     def knn_validate(self):
         return eval_utils.compute_neighbor_accuracy(*self.build_features(split="test"))
+
+    @torch.no_grad()
+    def cluster_validate(self):
+        """Cluster accuracy after Hungarian matching on the test-split features (the metric of the reference's README table): k-means with one cluster per
+        class; the optional config block ``cluster_eval: {niter, nredo, seed}`` overrides faiss.Kmeans's defaults (25, 1, 1234)."""
+        opts = {key: int(val) for key, val in (self.config.get("cluster_eval") or {}).items() if key in ("niter", "nredo", "seed")}
+        fvecs, labels = self.build_features(split="test")
+        return eval_utils.compute_cluster_accuracy(fvecs, labels, num_classes=self.test_loader.num_classes, device=self.device, **opts)
 
     def perform_linear_eval(self):
         sets = {}

@@ -805,6 +805,91 @@ def knn_label_agreement(z, labels, k):
     return int(count.item())
 
 
+# ------------------------------------------------------------------------------------------- k-means / cluster accuracy (csrc/kmeans.hip)
+def _kmeans_arith():
+    return _lib.ARITH_BF16X3 if ARITHMETIC == "bf16x3" else _lib.ARITH_F32_MFMA
+
+
+def _kmeans_operands(who, x, centroids):
+    """Checks shared by the two k-means calls; returns (x, centroids, n, d, k, dp) with dp the column count the kernels see (d rounded up to 4)."""
+    _lib._dev(x, centroids)
+    if x.dim() != 2 or centroids.dim() != 2 or x.dtype != torch.float32 or centroids.dtype != torch.float32:
+        raise _lib.SsvError(f"{who}: fp32 matrices x [n, d] and centroids [k, d] expected (got {tuple(x.shape)} {x.dtype}, {tuple(centroids.shape)} {centroids.dtype})")
+    if not x.is_contiguous() or not centroids.is_contiguous():
+        raise _lib.SsvError(f"{who}: x and centroids must be contiguous")
+    (n, d), (k, dc) = x.shape, centroids.shape
+    if dc != d:
+        raise _lib.SsvError(f"{who}: x has {d} columns, the centroids {dc}")
+    if not 1 <= k <= n:
+        raise _lib.SsvError(f"{who}: need 1 <= k <= n (got k = {k}, n = {n})")
+    if k > _lib.KMEANS_MAX_K or d > _lib.KMEANS_MAX_D or d < 1:
+        raise _lib.SsvError(f"{who}: k <= {_lib.KMEANS_MAX_K} and 1 <= d <= {_lib.KMEANS_MAX_D} (got k = {k}, d = {d})")
+    return n, d, k, (d + 3) // 4 * 4
+
+
+def _pad4(t, dp):
+    return t if t.shape[1] == dp else torch.nn.functional.pad(t, (0, dp - t.shape[1]))        # zero columns: exact
+
+
+def kmeans_prep(x, centroids):
+    """The buffer ssv_kmeans_assign / _update keep 1/2 |c|^2 and the centroids' bf16 planes in (caller-owned: it lives from an update to the next assignment)."""
+    n, d, k, dp = _kmeans_operands("kmeans_prep", x, centroids)
+    return torch.empty(_lib.load().ssv_kmeans_prep_bytes(dp, k), dtype=torch.uint8, device=x.device)
+
+
+def kmeans_assign(x, centroids, prep=None, prep_ready=False):
+    """labels [n] int32 = argmax_j (x . c_j - 1/2 |c_j|^2) (exact ties to the lowest j), dist [n] = squared distance to that centroid, counts [k] int32,
+    objective (0-d) = sum dist.  x [n, d], centroids [k, d]: contiguous fp32 device matrices; any d (columns are padded with zeros to a multiple of 4 here).
+    ``prep`` (kmeans_prep) with ``prep_ready``: the centroid-side operands kmeans_update left for exactly these centroids - they are not made again."""
+    n, d, k, dp = _kmeans_operands("kmeans_assign", x, centroids)
+    xp, cp = _pad4(x, dp), _pad4(centroids, dp)
+    lib = _lib.load()
+    if prep is None:
+        prep, prep_ready = torch.empty(lib.ssv_kmeans_prep_bytes(dp, k), dtype=torch.uint8, device=x.device), False
+    labels = torch.empty(n, dtype=torch.int32, device=x.device)
+    dist = torch.empty(n, dtype=torch.float32, device=x.device)
+    counts = torch.empty(k, dtype=torch.int32, device=x.device)
+    objective = torch.empty((), dtype=torch.float32, device=x.device)
+    arith = _kmeans_arith()
+    ws = workspace.get(lib.ssv_kmeans_workspace_bytes(n, dp, k, arith), x.device)
+    call("ssv_kmeans_assign", n, dp, k, ptr(xp), ptr(cp), ptr(prep), int(bool(prep_ready)), ptr(labels), ptr(dist), ptr(counts), ptr(objective), arith,
+         ptr(ws), ws.numel(), stream())
+    return labels, dist, counts, objective
+
+
+def kmeans_update(x, labels, counts, centroids, prep=None):
+    """In place: centroids[j] = mean of the rows of x labelled j (fixed summation order); counts[j] == 0 keeps centroids[j].  ``prep``: left ready for the next
+    kmeans_assign of these centroids."""
+    n, d, k, dp = _kmeans_operands("kmeans_update", x, centroids)
+    _lib._dev(labels, counts)
+    if labels.dtype != torch.int32 or counts.dtype != torch.int32 or labels.shape != (n,) or counts.shape != (k,) or not (labels.is_contiguous() and counts.is_contiguous()):
+        raise _lib.SsvError(f"kmeans_update: contiguous int32 labels [{n}] and counts [{k}] expected")
+    xp, cp = _pad4(x, dp), _pad4(centroids, dp)
+    lib = _lib.load()
+    arith = _kmeans_arith()
+    ws = workspace.get(lib.ssv_kmeans_workspace_bytes(n, dp, k, arith), x.device)
+    call("ssv_kmeans_update", n, dp, k, ptr(xp), ptr(labels), ptr(counts), ptr(cp), ptr(prep), arith, ptr(ws), ws.numel(), stream())
+    if cp is not centroids:
+        centroids.copy_(cp[:, :d])
+    invalidate_weight_caches()          # the centroids are a GEMM operand (the unfused assignment's filter bank) and changed in place
+    return centroids
+
+
+def cluster_votes(pred, targets, pred_k, targets_k):
+    """votes [pred_k, targets_k] int64: rows with pred == p and targets == t (the table hungarian_match counts on the host).  A label outside its range
+    raises SsvError (it is not counted; the device flag is read here - one synchronisation, this is an evaluation)."""
+    _lib._dev(pred, targets)
+    n = pred.numel()
+    if pred.dtype != torch.int32 or targets.dtype != torch.int32 or pred.dim() != 1 or targets.shape != pred.shape or not (pred.is_contiguous() and targets.is_contiguous()):
+        raise _lib.SsvError("cluster_votes: contiguous int32 vectors pred [n] and targets [n] expected")
+    votes = torch.empty((int(pred_k), int(targets_k)), dtype=torch.int64, device=pred.device)
+    flag = torch.empty(1, dtype=torch.int32, device=pred.device)
+    call("ssv_cluster_votes", n, ptr(pred), ptr(targets), int(pred_k), int(targets_k), ptr(votes), ptr(flag), stream())
+    if int(flag.item()) != 0:
+        raise _lib.SsvError(f"cluster_votes: a label lies outside [0, {int(pred_k)}) x [0, {int(targets_k)})")
+    return votes
+
+
 # ------------------------------------------------------------------------------------------- ViT / DINO pieces
 LN_EPS = 1e-5
 ATTENTION_BF16X3 = True      # the attention forward's two products in the bf16x3 arithmetic when ops.ARITHMETIC says so (the backward stays on the fp32 instruction)

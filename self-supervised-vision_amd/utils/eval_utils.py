@@ -3,6 +3,8 @@
 compute_neighbor_accuracy is the reference's 20-NN label agreement (utils/eval_utils.py:13-21, faiss.IndexFlatIP search) as
 one C-ABI call: S = Z Z^T on the fp32-MFMA GEMM kernel, streaming top-(k+1) per query on the GPU (csrc/evalknn.hip) - no faiss,
 and `eval_every` costs milliseconds.  linear_evaluation is a small closed loop on frozen features.
+kmeans / compute_cluster_accuracy: Lloyd's k-means on the GPU (csrc/kmeans.hip) and the cluster accuracy after Hungarian matching - the
+metric the reference's README reports and its code never computes (it has hungarian_match and a faiss.Kmeans run, nothing joins them).
 """
 import numpy as np
 import torch
@@ -32,6 +34,75 @@ def hungarian_match(preds, targets, preds_k, targets_k):
             votes[c1, c2] = int(((preds == c1) & (targets == c2)).sum())
     rows, cols = linear_sum_assignment(preds.shape[0] - votes)
     return list(zip(rows.tolist(), cols.tolist()))
+
+
+def _features_on_device(fvecs, device, who):
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{who} runs on the GPU (libssv_hip); no HIP device is visible and there is no CPU fallback")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    x = torch.as_tensor(fvecs, dtype=torch.float32).to(device).contiguous()
+    if x.dim() != 2:
+        raise ValueError(f"{who}: expected fvecs [n,d], got {tuple(x.shape)}")
+    return x, device
+
+
+def kmeans(fvecs, k, niter=25, nredo=1, seed=1234, device=None):
+    """Lloyd's k-means on the GPU (ops.kmeans_assign / ops.kmeans_update); the defaults are faiss.Kmeans's (niter 25, nredo 1, seed 1234).
+    Returns {"centroids" [k,d] fp32, "labels" [n] int32 (the assignment to the RETURNED centroids), "objective" (its sum of squared distances, a float),
+    "objectives" (one float per iteration of the winning run: the objective of the assignment that iteration's update was made from)}, tensors on the device.
+
+    Redo r starts from the rows torch.randperm(n, generator=torch.Generator().manual_seed(seed + r))[:k] and runs exactly ``niter`` iterations (assign, update) - no
+    early stop, no host synchronisation inside the loop: the objectives are gathered in a device array and read once per redo.  The run with the lowest FINAL
+    objective wins, the lower r on a tie.  Equal inputs give equal bits.
+
+    Where this departs from faiss.Kmeans (the reference's models/deep_cluster.py:100-118):
+      * a cluster that loses all its members KEEPS its centroid (faiss splits a large cluster to refill it);
+      * the initial centroids are drawn with torch.randperm as above, not with faiss's own generator: the same seed does not give faiss's start;
+      * every point takes part in every iteration (faiss subsamples to max_points_per_centroid = 256 points per centroid)."""
+    x, device = _features_on_device(fvecs, device, "kmeans")
+    n, k, niter, nredo = x.shape[0], int(k), int(niter), int(nredo)
+    if not 1 <= k <= n:
+        raise ValueError(f"kmeans: need 1 <= k <= n (got k = {k}, n = {n})")
+    if niter < 1 or nredo < 1:
+        raise ValueError(f"kmeans: niter and nredo must be at least 1 (got {niter}, {nredo})")
+    d = x.shape[1]
+    if d % 4:
+        x = torch.nn.functional.pad(x, (0, 4 - d % 4))            # once, not once per call: zero columns change no distance and stay zero in every mean
+    best = None
+    for r in range(nredo):
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + r))[:k].to(device)
+        centroids = x[rows].contiguous()
+        prep = ops.kmeans_prep(x, centroids)
+        trace = torch.empty(niter + 1, dtype=torch.float32, device=device)
+        ready = False
+        for it in range(niter):
+            labels, _, counts, objective = ops.kmeans_assign(x, centroids, prep=prep, prep_ready=ready)
+            trace[it].copy_(objective)
+            ops.kmeans_update(x, labels, counts, centroids, prep=prep)
+            ready = True
+        labels, _, _, objective = ops.kmeans_assign(x, centroids, prep=prep, prep_ready=True)      # the assignment to the centroids that are returned
+        trace[niter].copy_(objective)
+        trace = trace.cpu().tolist()                                                                # the one read of this redo
+        if best is None or trace[niter] < best["objective"]:
+            best = {"centroids": centroids[:, :d].contiguous(), "labels": labels, "objective": trace[niter], "objectives": trace[:niter], "redo": r}
+    return best
+
+
+def compute_cluster_accuracy(fvecs, targets, num_classes=None, niter=25, nredo=1, seed=1234, device=None):
+    """Cluster accuracy after Hungarian matching: k-means with k = num_classes (default targets.max() + 1) on the GPU, the cluster x class vote table on the GPU
+    (ops.cluster_votes), scipy's linear_sum_assignment(n - votes) as in hungarian_match, matched votes / n."""
+    from scipy.optimize import linear_sum_assignment
+    x, device = _features_on_device(fvecs, device, "compute_cluster_accuracy")
+    y = torch.as_tensor(targets).to(device=device, dtype=torch.int32).contiguous()
+    n = x.shape[0]
+    if y.shape != (n,):
+        raise ValueError(f"expected fvecs [n,d] and targets [n], got {tuple(x.shape)} and {tuple(y.shape)}")
+    if num_classes is None:
+        num_classes = int(y.max().item()) + 1
+    run = kmeans(x, int(num_classes), niter=niter, nredo=nredo, seed=seed, device=device)
+    votes = ops.cluster_votes(run["labels"], y, int(num_classes), int(num_classes)).cpu().numpy()
+    rows, cols = linear_sum_assignment(n - votes)
+    return float(votes[rows, cols].sum()) / float(n)
 
 
 def probe_batches(n, batch_size, epoch, shuffle, seed=420):
