@@ -430,6 +430,29 @@ int ssv_fill(int64_t n, float* p, float value, void* stream);
 /* dst[i] += src[i]  (gradient accumulation where no producer kernel can fuse it) */
 int ssv_add(int64_t n, float* dst, const float* src, void* stream);
 
+/* ---- optimizer: LARS (You et al. 2017), the optimizer of the large-batch SimCLR / BYOL / Barlow Twins recipes (csrc/lars.hip); the reference has none.
+ * Per tensor t of the arena, with flags decay_t and adapt_t:  u = (g + g2) + (decay_t ? wd : 0) p;  q_t = eta |p|_2 / |u|_2 if adapt_t and both norms > 0,
+ * else 1;  mu = momentum mu + q_t u (mu starts at zero: no first-step flag, no Nesterov);  p = p - lr mu.  Non-finite inputs get no special treatment.
+ * The plan (csrc/lars_plan.h) cuts the arena into chunks of at most ssv_lars_chunk_floats() floats that never cross a tensor: a chunk table (start, length,
+ * tensor) and a tensor table (first chunk, chunk count, flags), 16 bytes per record, chunk table first.  ssv_lars_plan_build is a pure HOST function: offset[T] and
+ * numel[T] (int64, floats), decay[T] and adapt[T] (int32, != 0 = on) are HOST arrays, `plan` a HOST buffer of ssv_lars_plan_bytes(T, numel) bytes that the caller
+ * uploads as it is (16-byte aligned); ssv_lars_plan_chunks is its chunk count.  Refused (the sizing helpers answer 0): T < 1, offsets that do not ascend,
+ * overlapping tensors, offsets that are not multiples of 4 floats, numel < 1, a buffer that is too small (SSV_ERR_WORKSPACE).  Floats between tensors
+ * (ParamArena's padding) belong to no chunk: they are not read into a norm and not written.
+ * ssv_lars_step: two launches, no host synchronisation, nothing from the host per step.  (1) one workgroup per chunk writes the chunk's partial sums of p^2 and
+ * u^2 into `ws` (ssv_lars_workspace_bytes(nchunks)); (2) one workgroup per chunk folds its tensor's partials in chunk order, in double - every workgroup of a tensor
+ * the same list in the same order, so all hold the same q_t bit for bit - and updates mu and p over its chunk; ratios[t] (device float [T]) receives q_t.  No
+ * floating-point atomics: equal inputs give equal bits.  hyper = (lr, weight decay, momentum, eta) in DEVICE memory, the only form: the step can be captured into a
+ * HIP graph as it stands.  n: floats in the arena (p, g, g2, mu); a plan record that points outside it is skipped.  g2 may be NULL. */
+int64_t ssv_lars_chunk_floats(void);
+int64_t ssv_lars_plan_chunks(int32_t T, const int64_t* numel_host);
+size_t ssv_lars_plan_bytes(int32_t T, const int64_t* numel_host);
+int ssv_lars_plan_build(int32_t T, const int64_t* offset_host, const int64_t* numel_host, const int32_t* decay_host, const int32_t* adapt_host,
+                        void* plan_host, size_t plan_bytes);
+size_t ssv_lars_workspace_bytes(int64_t nchunks);
+int ssv_lars_step(int64_t n, int32_t T, int64_t nchunks, const void* plan, float* p, const float* g, const float* g2, float* mu,
+                  const float* hyper /*[4]*/, float* ratios /*[T]*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- two-view augmentation (R1): the chain of configs/simclr.yaml:13-29 on the GPU ----------
  * replaces DoubleAugmentedDataset.__getitem__ utils/data_utils.py:68-73 / get_transform
  * utils/augmentations.py:128-144 (torchvision 0.9.1 + Pillow 8.3.1 in DataLoader workers).

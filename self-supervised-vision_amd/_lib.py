@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSV_HIP_LIB") or os.path.join(_HERE, "csrc", "libssv_hip.so")   # override: diagnostic builds only
 
-ABI_VERSION = 123        # ssv_version() of the library this binding was written against (include/ssv_hip.h)
+ABI_VERSION = 124       # ssv_version() of the library this binding was written against (include/ssv_hip.h)
 PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_fwd", "bn_bwd", "pool", "loss", "optim", "aug", "misc", "attn", "norm")
 
 
@@ -145,6 +145,12 @@ SIGNATURES = {
     "ssv_barlow_cgrad": (C.c_int, [_i32, _vp, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
     "ssv_sgd_nesterov": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, C.c_int, _vp]),
     "ssv_sgd_nesterov_dev": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ssv_lars_chunk_floats": (_i64, []),
+    "ssv_lars_plan_chunks": (_i64, [_i32, _vp]),
+    "ssv_lars_plan_bytes": (_sz, [_i32, _vp]),
+    "ssv_lars_plan_build": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "ssv_lars_workspace_bytes": (_sz, [_i64]),
+    "ssv_lars_step": (C.c_int, [_i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssv_ema": (C.c_int, [_i64, _vp, _vp, _f32, _vp]),
     "ssv_fill": (C.c_int, [_i64, _vp, _f32, _vp]),
     "ssv_add": (C.c_int, [_i64, _vp, _vp, _vp]),

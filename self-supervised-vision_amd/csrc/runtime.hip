@@ -13,7 +13,7 @@ void ssv_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ssv_version(void) { return 123; }   // 123: the k-means / cluster-vote entry points (kmeans.hip); 122: the gaussian_blur entry points (augment.hip); 121: the PIRL entry points (pirl.hip); 1.2x: round 6, ssv_conv_desc carries the arithmetic (SSV_ARITH_BF16X3) and the pre-split weight planes; earlier: 1.1x round 5 entry points
+extern "C" int ssv_version(void) { return 124; }   // 124: the LARS entry points (lars.hip); 123: the k-means / cluster-vote entry points (kmeans.hip); 122: the gaussian_blur entry points (augment.hip); 121: the PIRL entry points (pirl.hip); 1.2x: round 6, ssv_conv_desc carries the arithmetic (SSV_ARITH_BF16X3) and the pre-split weight planes; earlier: 1.1x round 5 entry points
 extern "C" const char* ssv_last_error(void) { return g_err; }
 #ifndef SSV_SRC_SHA16
 #define SSV_SRC_SHA16 "unknown"

@@ -135,15 +135,15 @@ class StepGraph:
         return {k: batch[k] for k in keys}
 
     def _why_not(self, ins):
-        from .utils.train_utils import FusedAdamW, FusedSGD
+        from .utils.train_utils import FusedAdamW, FusedLARS, FusedSGD
         if self.mode == "0":
             return "SSV_STEP_GRAPH=0"
         if not getattr(self.trainer, "graph_safe", False):
             return f"{type(self.trainer).__name__}.train_step keeps per-step state on the host (graph_safe is False)"
         if hdist.is_on():
             return "a process group is active (collectives stay eager)"
-        if not isinstance(getattr(self.trainer, "optim", None), (FusedSGD, FusedAdamW)):
-            return "the optimizer is neither the fused SGD nor the fused AdamW"
+        if not isinstance(getattr(self.trainer, "optim", None), (FusedSGD, FusedAdamW, FusedLARS)):
+            return "the optimizer is neither the fused SGD nor the fused AdamW nor the fused LARS"
         if not ins or not all(t.is_cuda for t in ins.values()):
             return "the batch is not on the GPU"
         if self.mode == "auto" and max(t.shape[-1] * t.shape[-2] for t in ins.values()) > AUTO_MAX_PIXELS:
@@ -155,7 +155,7 @@ class StepGraph:
         the trainer names in ``graph_key()`` (DINO: temperatures, centre momentum)."""
         g = self.trainer.optim.param_groups[0]
         opt = tuple(sorted((k, float(v) if isinstance(v, (int, float)) else tuple(float(x) for x in v)) for k, v in g.items()
-                           if k in ("betas", "eps")))            # lr / weight decay / momentum are device memory (optim.push_hyper): not part of the key
+                           if k in ("betas", "eps")))            # lr / weight decay / momentum (and LARS's eta) are device memory (optim.push_hyper): not part of the key
         extra = tuple(self.trainer.graph_key()) if hasattr(self.trainer, "graph_key") else ()
         # ... and the arithmetic: it selects kernels AND (round 6) dispatch thresholds, so a step captured under one never replays under the other (ops.arithmetic())
         return (tuple((k, tuple(t.shape), t.stride()) for k, t in sorted(ins.items())), opt, float(getattr(self.trainer.optim, "clip", 0.0)), extra, ops.ARITHMETIC)
