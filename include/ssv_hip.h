@@ -543,6 +543,49 @@ int ssv_kmeans_update(int64_t n, int32_t d, int32_t k, const float* x, const int
 int ssv_cluster_votes(int64_t n, const int32_t* pred, const int32_t* targets, int32_t pred_k, int32_t targets_k, int64_t* votes, int32_t* flag,
                       void* stream);
 
+/* ---- the weighted kNN classifier (csrc/knnclassify.hip): the evaluation of InstDisc / MoCo / DINO's eval_knn - every TEST feature searches the TRAIN bank, its k
+ * best neighbours vote for their class with weight exp(similarity / T).  The reference has no such metric (its compute_neighbor_accuracy above searches a set against
+ * itself and counts label agreement).  Two calls: an exact top-k inner-product search of one matrix against another, and the vote over its result.
+ *
+ * ssv_knn_search: queries [m][d], bank [n][d] fp32, dense.  For every query i the k bank rows j with the largest s_ij = q_i . b_j, as sim [m][k] fp32 and
+ * idx [m][k] int32, SORTED:
+ *   order  s descending; exact ties (equal floats, -0 == +0) to the LOWER j; a NaN score ranks below every number (-inf included), NaNs among themselves by
+ *          ascending j.  sim carries the bits the product produced (a NaN stays that NaN).
+ *   limits 1 <= k <= min(n, SSV_KNN_MAX_K); d % 4 == 0 (pad with zero columns: exact) and d <= SSV_KNN_MAX_D; 1 <= m <= 2^30; n < 2^31.  Anything else is refused
+ *          with SSV_ERR_INVALID and a message; nothing is clamped.
+ *   product  S = Q B^T is formed in the workspace by ssv_conv2d_fwd (the bank part as a 1x1 filter bank), chunk_rows query rows by part_cols bank rows at a time, in
+ *          `arithmetic` (SSV_ARITH_F32_MFMA | SSV_ARITH_BF16X3).  SSV_ARITH_BF16X3 needs d % 32 == 0 and n % 4 == 0 and part_cols % 4 == 0 (16-byte rows of every
+ *          part of S); a call without them runs WHOLLY on fp32 MFMA, as ssv_knn_label_agreement_arith does for its widths.  The selection is not fused into the
+ *          product.  Bit-identical bank rows score bit-identically within a call (one instruction sequence per column), so a duplicate never outranks its first copy.
+ *   selection  exact: one workgroup per row of S, a radix select over order-preserving 32-bit keys (four 8-bit digits, integer LDS histograms), one gather pass for
+ *          the strictly greater scores, the lowest-index ties of the k-th score, a sort of the <= 1024 (key, index) pairs in LDS.  No floating-point atomics; equal
+ *          inputs give equal bits.
+ *   partition  chunk_rows / part_cols: 0 = the library's choice (1024 rows; equal parts of at most min(65536, 2^26 / d) columns), any other value is taken as given
+ *          (a value above m / n means one chunk / one part) and refused if a chunk of S would break the GEMM's limits (chunk_rows * part_cols and chunk_rows * d
+ *          below 2^29 - 2^22, part_cols * d below 2^29).  A bank wider than one part is searched part by part: each part's sorted top-min(k, its columns) is merged
+ *          into the running result (sim / idx themselves) under the same order rule.
+ *   workspace  ssv_knn_search_workspace_bytes(same shape and partition arguments): one chunk of S, the bf16 planes of one part, one chunk of part results - with the
+ *          default partition at most 256 MiB + 384 MiB + 8 MiB whatever n is.  0 for a shape the search refuses.
+ * ssv_knn_vote: sim / idx [m][k] as the search returns them, bank_labels [n] int32, C = num_classes.
+ *   score_i[c] = sum over ranks r with bank_labels[idx_ir] == c of exp((sim_ir - sim_i0) * inv_temp), summed in rank order r = 0, 1, ... by one thread per class (expf;
+ *   no atomics).  sim_i0 is the row's best similarity: the common factor exp(-sim_i0 / T) it takes out changes no arg-max and keeps unnormalised features from
+ *   overflowing - scores are the InstDisc weights divided by the largest one, in (0, k].
+ *   pred [m][topn] int32: the topn classes by score descending, ties to the LOWER class (a class without votes scores 0 and ranks by its number).  scores [m][C]
+ *   fp32 is optional (NULL).  An idx outside [0, n) or a label outside [0, C) is not counted and sets *flag (device int32, zeroed by the call); an entry whose sim
+ *   is NaN is not counted.  Limits: 1 <= m <= 2^30, 1 <= k <= SSV_KNN_MAX_K, 1 <= n < 2^31, 1 <= C <= SSV_KNN_MAX_CLASSES, 1 <= topn <= min(C, SSV_KNN_MAX_TOPN),
+ *   inv_temp finite and positive; the outputs alias neither each other nor an input.
+ * Not built: a search fused into the product, approximate search, exclusion of the query itself, k > 1024.
+ * The ABI version stays 124: entry points were only added, and the binding refuses a library that lacks a declared symbol when it loads. */
+#define SSV_KNN_MAX_K 1024
+#define SSV_KNN_MAX_D 8192
+#define SSV_KNN_MAX_CLASSES 4096
+#define SSV_KNN_MAX_TOPN 8
+size_t ssv_knn_search_workspace_bytes(int64_t m, int64_t n, int32_t d, int32_t k, int32_t arithmetic, int32_t chunk_rows, int32_t part_cols);
+int ssv_knn_search(int64_t m, int64_t n, int32_t d, int32_t k, const float* queries, const float* bank, float* sim, int32_t* idx,
+                   int32_t arithmetic, int32_t chunk_rows, int32_t part_cols, void* ws, size_t ws_bytes, void* stream);
+int ssv_knn_vote(int64_t m, int32_t k, int64_t n, int32_t num_classes, int32_t topn, const float* sim, const int32_t* idx, const int32_t* bank_labels,
+                 float inv_temp, int32_t* pred, float* scores, int32_t* flag, void* stream);
+
 /* ==== "next" row 1 of the scope table: DINO on the reference's ViT (networks/vit.py, models/dino.py) ====================
  * Linear layers of the encoder and of the projection head are ssv_conv2d_fwd/dgrad/wgrad with H = W = R = S = 1 over
  * N = B*T token rows; what follows are the pieces that are not GEMMs.  All matrices are dense row-major fp32. */

@@ -22,6 +22,7 @@ class SsvError(RuntimeError):
 ARITH_F32_MFMA, ARITH_BF16X3 = 0, 6      # ssv_conv_desc.arithmetic (include/ssv_hip.h)
 BLUR_MAX_PIXELS, BLUR_MAX_SIGMA = 81920, 1000.0      # SSV_BLUR_MAX_PIXELS, SSV_BLUR_MAX_SIGMA (include/ssv_hip.h)
 KMEANS_MAX_K, KMEANS_MAX_D = 4096, 8192              # SSV_KMEANS_MAX_K, SSV_KMEANS_MAX_D (include/ssv_hip.h)
+KNN_MAX_K, KNN_MAX_D, KNN_MAX_CLASSES, KNN_MAX_TOPN = 1024, 8192, 4096, 8      # SSV_KNN_MAX_* (include/ssv_hip.h)
 
 
 class ConvDesc(C.Structure):
@@ -171,6 +172,9 @@ SIGNATURES = {
     "ssv_kmeans_assign": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "ssv_kmeans_update": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "ssv_cluster_votes": (C.c_int, [_i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ssv_knn_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "ssv_knn_search": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ssv_knn_vote": (C.c_int, [_i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
     "ssv_vit_embed_fwd": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ssv_vit_embed_bwd": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "ssv_layernorm_fwd": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),

@@ -3,9 +3,12 @@
 The flag surface is the reference's (main.py:11-12,38-43), verbatim: -c/--config, -m/--arch, -a/--algo, -t/--task,
 -o/--output, -l/--load with the same choices, so scripts written for the reference keep working.  Algorithms outside the
 accelerated path (deep_cluster, swav, sela) stay on the
-surface and raise NotImplementedError.  One task is added to the reference's three: `-t cluster_eval -l <dir>` loads a checkpoint, runs
+surface and raise NotImplementedError.  Two tasks are added to the reference's three: `-t cluster_eval -l <dir>` loads a checkpoint, runs
 k-means on the test-split features with one cluster per class and logs the cluster accuracy after Hungarian matching - the metric of the
-reference's README table, which the reference's own code never computes (optional config block `cluster_eval: {niter, nredo, seed}`).  Multi-GPU: `SSV_GPUS=N python main.py ...` (the repo-root script starts its N ranks itself,
+reference's README table, which the reference's own code never computes (optional config block `cluster_eval: {niter, nredo, seed}`);
+`-t knn_eval -l <dir>` loads a checkpoint and logs the top-1 / top-5 accuracy of the weighted kNN classifier (InstDisc / MoCo / DINO's eval_knn:
+the test-split features search the train-split features, the k best neighbours vote with weight exp(similarity / T); optional config block
+`knn_eval: {k, temperature}`, defaults 20 and 0.07).  Multi-GPU: `SSV_GPUS=N python main.py ...` (the repo-root script starts its N ranks itself,
 ssv_amd/launch.py) or `python -m torch.distributed.run --nproc-per-node N main.py ...`.
 """
 import argparse
@@ -15,7 +18,7 @@ import time
 
 import numpy as np
 
-TASKS = ("train", "linear_eval", "get_features", "cluster_eval")
+TASKS = ("train", "linear_eval", "get_features", "cluster_eval", "knn_eval")
 NETWORKS = ("resnet18", "resnet50", "resnext50", "resnext101", "wide_resnet50", "wide_resnet101", "vit")
 # algo -> (module, class) for what is built; None marks flag values that exist but are not accelerated
 ALGORITHMS = {"simclr": ("simclr", "SimCLR"), "moco": ("moco", "MoCo"), "byol": ("byol", "BYOL"), "dino": ("dino", "DINO"), "pirl": ("pirl", "PIRL"),
@@ -63,6 +66,10 @@ def main(argv=None):
         model.perform_linear_eval()
     elif args["task"] == "cluster_eval":
         model.logger.write("Test cluster accuracy: {:.4f}".format(model.cluster_validate()), mode="info")
+    elif args["task"] == "knn_eval":
+        res = model.knn_classify_validate()
+        top5 = float("nan") if res["top5"] is None else res["top5"]               # fewer than 5 classes
+        model.logger.write("Test kNN classifier accuracy: top-1 {:.4f} top-5 {:.4f}".format(res["top1"], top5), mode="info")
     else:   # get_features: <split>_fvecs.npy / <split>_gt.npy in the run directory (binary files; the reference opens them in text mode)
         for split in ("train", "test"):
             fvecs, gt = model.build_features(split=split)

@@ -3,7 +3,7 @@
 The reference carries one ~170-line trainer per algorithm (models/simclr.py:39-167 and its siblings); on this path the
 common part exists once and an algorithm supplies four hooks (`_build`, `_embed`, `_checkpoint_state`, `_load_state`)
 plus `train_step`.  What callers of the reference rely on is kept: ``Cls(args: dict)``; ``train()``,
-``train_step(batch) -> {"loss": float}``, ``knn_validate()``, ``cluster_validate()``, ``build_features(split)``, ``perform_linear_eval()``,
+``train_step(batch) -> {"loss": float}``, ``knn_validate()``, ``cluster_validate()``, ``knn_classify_validate()``, ``build_features(split)``, ``perform_linear_eval()``,
 ``save_checkpoint()``, ``load_checkpoint(dir)``, ``adjust_learning_rate(epoch)``; attributes ``config, output_dir, logger,
 device, optim, scheduler, loss_fn, best_metric``; the log-line formats; ``best_model.pt`` in the run directory.
 """
@@ -162,6 +162,16 @@ class TwoViewTrainer:
         opts = {key: int(val) for key, val in (self.config.get("cluster_eval") or {}).items() if key in ("niter", "nredo", "seed")}
         fvecs, labels = self.build_features(split="test")
         return eval_utils.compute_cluster_accuracy(fvecs, labels, num_classes=self.test_loader.num_classes, device=self.device, **opts)
+
+    @torch.no_grad()
+    def knn_classify_validate(self):
+        """The weighted kNN classifier (eval_utils.knn_classify): the test-split features search the train-split features; returns {"top1", "top5", "pred"}.
+        The optional config block ``knn_eval: {k, temperature}`` overrides the defaults (20, 0.07)."""
+        block = self.config.get("knn_eval") or {}
+        opts = {key: cast(block[key]) for key, cast in (("k", int), ("temperature", float)) if key in block}
+        train_fvecs, train_labels = self.build_features(split="train")
+        test_fvecs, test_labels = self.build_features(split="test")
+        return eval_utils.knn_classify(train_fvecs, train_labels, test_fvecs, test_labels, num_classes=self.train_loader.num_classes, device=self.device, **opts)
 
     def perform_linear_eval(self):
         sets = {}

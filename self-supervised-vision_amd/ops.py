@@ -890,6 +890,57 @@ def cluster_votes(pred, targets, pred_k, targets_k):
     return votes
 
 
+# ------------------------------------------------------------------------------------------- weighted kNN classifier (csrc/knnclassify.hip)
+def knn_search(queries, bank, k, chunk_rows=0, part_cols=0):
+    """(sim [m, k] fp32, idx [m, k] int32): for every row of queries [m, d] the k rows of bank [n, d] with the largest inner product, sorted - similarity
+    descending, exact ties to the lower index, a NaN below every number.  Contiguous fp32 device matrices of any d (columns are padded with zeros to a multiple
+    of 4 here: exact); 1 <= k <= min(n, 1024).  ``chunk_rows`` / ``part_cols``: query rows and bank rows of one block of the product (0: the library's choice)."""
+    _lib._dev(queries, bank)
+    if queries.dim() != 2 or bank.dim() != 2 or queries.dtype != torch.float32 or bank.dtype != torch.float32:
+        raise _lib.SsvError(f"knn_search: fp32 matrices queries [m, d] and bank [n, d] expected (got {tuple(queries.shape)} {queries.dtype}, {tuple(bank.shape)} {bank.dtype})")
+    if not queries.is_contiguous() or not bank.is_contiguous():
+        raise _lib.SsvError("knn_search: queries and bank must be contiguous")
+    (m, d), (n, db), k = queries.shape, bank.shape, int(k)
+    if db != d or d < 1 or d > _lib.KNN_MAX_D:
+        raise _lib.SsvError(f"knn_search: queries have {d} columns, the bank {db}; 1 <= d <= {_lib.KNN_MAX_D}")
+    if m < 1 or not 1 <= k <= min(n, _lib.KNN_MAX_K):
+        raise _lib.SsvError(f"knn_search: need m >= 1 and 1 <= k <= min(n, {_lib.KNN_MAX_K}) (got m = {m}, n = {n}, k = {k})")
+    dp = (d + 3) // 4 * 4
+    qp, bp = _pad4(queries, dp), _pad4(bank, dp)
+    arith = _kmeans_arith()
+    need = _lib.load().ssv_knn_search_workspace_bytes(m, n, dp, k, arith, int(chunk_rows), int(part_cols))
+    ws = workspace.get(max(need, 16), queries.device)                   # need == 0: a partition the library refuses - the call below says why
+    sim = torch.empty((m, k), dtype=torch.float32, device=queries.device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=queries.device)
+    call("ssv_knn_search", m, n, dp, k, ptr(qp), ptr(bp), ptr(sim), ptr(idx), arith, int(chunk_rows), int(part_cols), ptr(ws), ws.numel(), stream())
+    return sim, idx
+
+
+def knn_vote(sim, idx, bank_labels, num_classes, temperature, topn=1, return_scores=False):
+    """pred [m, topn] int32: per row of (sim, idx) [m, k] (what knn_search returns) the ``topn`` classes by score descending, ties to the lower class, with
+    score[c] = sum over the neighbours labelled c of exp((sim - sim[:, 0]) / temperature), summed in rank order.  ``return_scores``: (pred, scores [m, C] fp32).
+    bank_labels [n] int32.  An index outside the bank or a label outside [0, num_classes) raises SsvError (it is not counted; the device flag is read here -
+    one synchronisation, this is an evaluation)."""
+    _lib._dev(sim, idx, bank_labels)
+    if sim.dim() != 2 or sim.dtype != torch.float32 or idx.dtype != torch.int32 or idx.shape != sim.shape or not (sim.is_contiguous() and idx.is_contiguous()):
+        raise _lib.SsvError("knn_vote: contiguous sim [m, k] fp32 and idx [m, k] int32 expected")
+    if bank_labels.dim() != 1 or bank_labels.dtype != torch.int32 or not bank_labels.is_contiguous():
+        raise _lib.SsvError("knn_vote: a contiguous int32 vector bank_labels [n] expected")
+    (m, k), n, c, topn = sim.shape, bank_labels.numel(), int(num_classes), int(topn)
+    if not (float(temperature) > 0.0 and math.isfinite(1.0 / float(temperature))):
+        raise _lib.SsvError(f"knn_vote: the temperature must be positive and finite (got {temperature})")
+    if m < 1 or not 1 <= k <= _lib.KNN_MAX_K or n < 1 or not 1 <= c <= _lib.KNN_MAX_CLASSES or not 1 <= topn <= min(c, _lib.KNN_MAX_TOPN):
+        raise _lib.SsvError(f"knn_vote: need m >= 1, 1 <= k <= {_lib.KNN_MAX_K}, n >= 1, 1 <= num_classes <= {_lib.KNN_MAX_CLASSES}, 1 <= topn <= min(num_classes, "
+                            f"{_lib.KNN_MAX_TOPN}) (got m = {m}, k = {k}, n = {n}, num_classes = {c}, topn = {topn})")
+    pred = torch.empty((m, topn), dtype=torch.int32, device=sim.device)
+    scores = torch.empty((m, c), dtype=torch.float32, device=sim.device) if return_scores else None
+    flag = torch.empty(1, dtype=torch.int32, device=sim.device)
+    call("ssv_knn_vote", m, k, n, c, topn, ptr(sim), ptr(idx), ptr(bank_labels), 1.0 / float(temperature), ptr(pred), ptr(scores), ptr(flag), stream())
+    if int(flag.item()) != 0:
+        raise _lib.SsvError(f"knn_vote: a neighbour index lies outside [0, {n}) or a bank label outside [0, {c})")
+    return (pred, scores) if return_scores else pred
+
+
 # ------------------------------------------------------------------------------------------- ViT / DINO pieces
 LN_EPS = 1e-5
 ATTENTION_BF16X3 = True      # the attention forward's two products in the bf16x3 arithmetic when ops.ARITHMETIC says so (the backward stays on the fp32 instruction)

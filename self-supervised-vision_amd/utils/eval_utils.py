@@ -5,6 +5,8 @@ one C-ABI call: S = Z Z^T on the fp32-MFMA GEMM kernel, streaming top-(k+1) per 
 and `eval_every` costs milliseconds.  linear_evaluation is a small closed loop on frozen features.
 kmeans / compute_cluster_accuracy: Lloyd's k-means on the GPU (csrc/kmeans.hip) and the cluster accuracy after Hungarian matching - the
 metric the reference's README reports and its code never computes (it has hungarian_match and a faiss.Kmeans run, nothing joins them).
+knn_classify: the weighted kNN classifier of InstDisc / MoCo / DINO (test features search the TRAIN bank, the k best neighbours vote with weight
+exp(similarity / T); csrc/knnclassify.hip) - top-1 / top-5 accuracy without any training.  The reference has no such metric.
 """
 import numpy as np
 import torch
@@ -103,6 +105,33 @@ def compute_cluster_accuracy(fvecs, targets, num_classes=None, niter=25, nredo=1
     votes = ops.cluster_votes(run["labels"], y, int(num_classes), int(num_classes)).cpu().numpy()
     rows, cols = linear_sum_assignment(n - votes)
     return float(votes[rows, cols].sum()) / float(n)
+
+
+def knn_classify(train_fvecs, train_labels, test_fvecs, test_labels, k=20, temperature=0.07, num_classes=None, normalize=True, device=None):
+    """The weighted k-nearest-neighbour classifier of InstDisc / MoCo / DINO's eval_knn: every test feature searches the TRAIN features (ops.knn_search, exact
+    inner product), its k best neighbours vote for their class with weight exp(similarity / temperature) (ops.knn_vote).  numpy arrays or device tensors;
+    rows are L2-normalised first (ssv_l2norm_fwd) unless ``normalize`` is False; k is clipped to the number of train rows (tiny synthetic sets);
+    ``num_classes`` defaults to train_labels.max() + 1.  Returns {"top1", "top5", "pred"}: accuracies as floats (top5 None with fewer than 5 classes) and
+    pred [m, min(5, num_classes)] int32 on the device, best class first - bit for bit what the two ops calls give when composed by hand."""
+    bank, device = _features_on_device(train_fvecs, device, "knn_classify")
+    queries, _ = _features_on_device(test_fvecs, device, "knn_classify")
+    ytr = torch.as_tensor(train_labels).to(device=device, dtype=torch.int32).contiguous()
+    yte = torch.as_tensor(test_labels).to(device=device, dtype=torch.int32).contiguous()
+    (n, d), m = bank.shape, queries.shape[0]
+    if queries.shape[1] != d or ytr.shape != (n,) or yte.shape != (m,):
+        raise ValueError(f"knn_classify: expected train [n,d] / [n] and test [m,d] / [m], got {tuple(bank.shape)} / {tuple(ytr.shape)} and {tuple(queries.shape)} / {tuple(yte.shape)}")
+    if num_classes is None:
+        num_classes = int(ytr.max().item()) + 1
+    num_classes, k = int(num_classes), max(1, min(int(k), n))
+    if normalize:
+        bank, queries = ops.l2norm_fwd(bank)[0], ops.l2norm_fwd(queries)[0]
+    sim, idx = ops.knn_search(queries, bank, k)
+    topn = min(5, num_classes)
+    pred = ops.knn_vote(sim, idx, ytr, num_classes, temperature, topn=topn)
+    hit = pred == yte[:, None]
+    top1 = float(hit[:, 0].sum().item()) / float(m)
+    top5 = float(hit.any(1).sum().item()) / float(m) if num_classes >= 5 else None
+    return {"top1": top1, "top5": top5, "pred": pred}
 
 
 def probe_batches(n, batch_size, epoch, shuffle, seed=420):
