@@ -246,7 +246,7 @@ aug_prep_k(int B, int Hs, int Ws, int Ho, int Wo, const uint8_t* __restrict__ sr
   }
   red[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(red);
   if (threadIdx.x == 0) cmean[vb] = need ? (int)((double)red[0] / (double)(Hs * Ws) + 0.5) : 0;
 }
 

@@ -54,6 +54,28 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// arg-max over a wave in the library's one order: value descending, the LOWER index on equal values (the first maximum, like argmax).  STEP is one exchange
+// with lane ^ o; WAVE the whole butterfly, after which all 64 lanes hold the winner.  Macros on purpose: the compiler simplifies a function's body before it
+// inlines it, and every kernel that moved to a function form came out with a different instruction schedule than the loop written in place.
+#define SSV_ARGMAX_FIRST_STEP(v, i, o) do { \
+    const float ov_ = __shfl_xor((v), (o), 64); \
+    const int oi_ = __shfl_xor((i), (o), 64); \
+    if (ov_ > (v) || (ov_ == (v) && oi_ < (i))) { (v) = ov_; (i) = oi_; } } while (0)
+#define SSV_WAVE_ARGMAX_FIRST(v, i) _Pragma("unroll") for (int o_ = 32; o_ > 0; o_ >>= 1) SSV_ARGMAX_FIRST_STEP(v, i, o_)
+// sum of sm[0 .. 255] into sm[0] by a 256-thread workgroup: a fixed tree (the order of additions is part of every caller's result).  Every thread has written
+// sm[threadIdx.x] and passed a barrier before; ends with a barrier.  A macro for the reason above.
+#define SSV_BLOCK_SUM_256(sm) \
+  for (int o_ = 128; o_ > 0; o_ >>= 1) { if ((int)threadIdx.x < o_) (sm)[threadIdx.x] += (sm)[threadIdx.x + o_]; __syncthreads(); }
+
+static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }           // workspace sections start on 256-byte boundaries
+
+// the 1x1 "convolution" that is the GEMM Y[rows, K] = X[rows, C] W[K, C]^T (w_planes: W pre-split by ssv_split_planes, or null)
+static inline ssv_conv_desc gemm_conv_desc(int rows, int C, int K, int arithmetic, const void* w_planes = nullptr) {
+  ssv_conv_desc cd = {};
+  cd.arithmetic = arithmetic; cd.w_planes = w_planes;
+  cd.N = rows; cd.H = 1; cd.W = 1; cd.C = C; cd.K = K; cd.R = 1; cd.S = 1; cd.stride = 1; cd.pad = 0; cd.Ho = 1; cd.Wo = 1;
+  return cd;
+}
 
 // ---- nn.GELU() in its erf form (networks/vit.py:38, models/dino.py:30-33) --------------------------------------------------------
 // erf in ~20 VALU instructions (the libm erff costs ~50 and branches): x * P5(x^2) for |x| < 1 (relative error 2e-7), 1 - u P4(u) exp(-x^2) with

@@ -83,7 +83,7 @@ __global__ void dino_loss_reduce_k(int64_t rows, const double* __restrict__ part
   for (int64_t i = threadIdx.x; i < rows; i += 256) a += partial[i];
   sh[threadIdx.x] = a;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sh);
   if (threadIdx.x == 0) { const float v = (float)(sh[0] * (double)scale); *loss = accumulate ? *loss + v : v; }
 }
 

@@ -76,12 +76,7 @@ __global__ void __launch_bounds__(256) knn_agree_k(const float* __restrict__ S, 
   for (int t = 0; t <= k; ++t) {
     float bv = val[0];
     int bi = idx[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
+    SSV_WAVE_ARGMAX_FIRST(bv, bi);
     if (bi == INT_MAX) break;                               // fewer than k+1 candidates
     if (idx[0] == bi) {                                     // the winning lane pops its head
 #pragma unroll
@@ -116,14 +111,6 @@ template <int D> __device__ __forceinline__ int kp_off(int key, int chunk) {    
   constexpr int CH = D / 8, RPW = 16 / CH;
   return key * (2 * D) + ((chunk ^ ((key / RPW) & (CH - 1))) << 4);
 }
-__device__ __forceinline__ int colof(int j, int half) { return (j & 3) + 8 * (j >> 2) + 4 * half; }
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8 (&pl)[3]) {
-  u32x2 pa[3], pb[3];
-  splitbf::split4(a, pa);
-  splitbf::split4(b, pb);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) pl[q] = __builtin_bit_cast(bf16x8, u32x4{pa[q][0], pa[q][1], pb[q][0], pb[q][1]});
-}
 // a precedes b in the result order (bitwise on purpose: three compares and two mask operations, no short-circuit branches)
 __device__ __forceinline__ bool before(float av, int ai, float bv, int bi) { return (av > bv) | ((av == bv) & (ai < bi)); }
 // (x, xi) into the sorted list; entries are distinct, empties are (-inf, INT_MAX) and an empty offer changes nothing.  Every new slot is a function of the OLD slots
@@ -156,7 +143,7 @@ knn_fused_k(const float* __restrict__ Z, int n, int cols_per_part, float* __rest
   {
     const float* qp = Z + (int64_t)min(q0 + c, n - 1) * D + 8 * half;
 #pragma unroll
-    for (int s = 0; s < D / 16; ++s) split8(*(const f32x4*)(qp + 16 * s), *(const f32x4*)(qp + 16 * s + 4), qf[s]);
+    for (int s = 0; s < D / 16; ++s) splitbf::split8(*(const f32x4*)(qp + 16 * s), *(const f32x4*)(qp + 16 * s + 4), qf[s]);
   }
   u32x2 (*wq)[DEPTH] = cb[wave];
   u32x2* wl = ls[wave][c];
@@ -239,9 +226,7 @@ knn_fused_k(const float* __restrict__ Z, int n, int cols_per_part, float* __rest
 #pragma unroll
         for (int q = 0; q < 3; ++q) kf[(sl + 1) & 1][q] = *(const bf16x8*)(kp + q * PL + kp_off<D>(c, 2 * (sl + 1) + half));
       }
-#define SSV_MM(P, Q_) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[sl & 1][P], qf[sl][Q_], s, 0, 0, 0)
-      SSV_MM(2, 0); SSV_MM(0, 2); SSV_MM(1, 1); SSV_MM(1, 0); SSV_MM(0, 1); SSV_MM(0, 0);          // smallest terms first
-#undef SSV_MM
+      splitbf::mma6_32(s, kf[sl & 1], qf[sl]);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (want && __ballot(cnt != 0)) drain();                    // some wave's queue filled up during the last tile: all four waves drain NOW, side by side - drains one
@@ -259,7 +244,7 @@ knn_fused_k(const float* __restrict__ Z, int n, int cols_per_part, float* __rest
           for (int j = 4 * g; j < 4 * g + 4; ++j) {
             const bool ge = s[j] >= thr_v;
             if (__ballot(ge)) {
-              const int col = k0 + colof(j, half);
+              const int col = k0 + splitbf::acc32_row(j, half);
               const bool in = ge && col < col_end && before(s[j], col, thr_v, thr_i);
               const bool room = cnt < DEPTH;
               if (in && room) { wq[lane][cnt] = u32x2{__float_as_uint(s[j]), (unsigned)col}; ++cnt; }
@@ -278,7 +263,7 @@ knn_fused_k(const float* __restrict__ Z, int n, int cols_per_part, float* __rest
           float v = s[0];
 #pragma unroll
           for (int jj = 1; jj < 16; ++jj) v = j == jj ? s[jj] : v;
-          const int col = k0 + colof(j, half);
+          const int col = k0 + splitbf::acc32_row(j, half);
           if (has && before(v, col, thr_v, thr_i)) { wq[lane][cnt] = u32x2{__float_as_uint(v), (unsigned)col}; ++cnt; }
         }
       }
@@ -346,12 +331,7 @@ __global__ void __launch_bounds__(256) softmax_ce_k(int N, int C, int ld, const 
   float mx = -INFINITY;
   int arg = 0;
   for (int c = lane; c < C; c += 64) { const float v = row[c]; if (v > mx) { mx = v; arg = c; } }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(mx, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (ov > mx || (ov == mx && oa < arg)) { mx = ov; arg = oa; }          // first maximum, like argmax
-  }
+  SSV_WAVE_ARGMAX_FIRST(mx, arg);
   float sm = 0.f;
   for (int c = lane; c < C; c += 64) sm += expf(row[c] - mx);
   sm = wave_sum(sm);
@@ -438,7 +418,7 @@ extern "C" int ssv_knn_label_agreement_arith(int64_t n, int32_t d, const float* 
   }
   void* planes = nullptr;
   if (arithmetic == SSV_ARITH_BF16X3) {
-    planes = (char*)ws + ((ssv_knn_workspace_bytes(n) + 255) & ~(size_t)255);
+    planes = (char*)ws + up256(ssv_knn_workspace_bytes(n));
     if (int rc = ssv_split_planes(n * d, z, planes, stream)) return rc;
   }
   {
@@ -447,9 +427,7 @@ extern "C" int ssv_knn_label_agreement_arith(int64_t n, int32_t d, const float* 
   }
   for (int64_t r0 = 0; r0 < n; r0 += cr) {
     const int rows = (int)((n - r0 < cr) ? (n - r0) : cr);
-    ssv_conv_desc cd = {};
-    cd.arithmetic = arithmetic; cd.w_planes = planes;
-    cd.N = rows; cd.H = 1; cd.W = 1; cd.C = d; cd.K = (int32_t)n; cd.R = 1; cd.S = 1; cd.stride = 1; cd.pad = 0; cd.Ho = 1; cd.Wo = 1;
+    ssv_conv_desc cd = gemm_conv_desc(rows, d, (int)n, arithmetic, planes);
     if (int rc = ssv_conv2d_fwd(&cd, z + r0 * d, z, nullptr, nullptr, S, stream)) return rc;      // S[rows, n] = Z[r0:r0+rows] Z^T
     ProfScope ps(SSV_PROF_MISC, s);
     const dim3 grid((unsigned)cdiv(rows, 4));

@@ -32,17 +32,9 @@ struct Geo { int T, S4, kpad; size_t hc_bytes, plane_bytes; };  // T tiles of 32
 inline Geo geo(int d, int k) {
   Geo g;
   g.T = cdiv(k, 32); g.S4 = cdiv(d, 64) * 4; g.kpad = g.T * 32;
-  g.hc_bytes = ((size_t)g.kpad * 4 + 255) & ~(size_t)255;
+  g.hc_bytes = up256((size_t)g.kpad * 4);
   g.plane_bytes = (size_t)g.S4 * g.T * 1024;
   return g;
-}
-
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8 (&pl)[3]) {
-  u32x2 pa[3], pb[3];
-  splitbf::split4(a, pa);
-  splitbf::split4(b, pb);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) pl[q] = __builtin_bit_cast(bf16x8, u32x4{pa[q][0], pa[q][1], pb[q][0], pb[q][1]});
 }
 
 // blocks [0, S4 * T / 4): the planes in fragment order, one (slab, tile) per wave; blocks behind: hc[j] = 1/2 |c_j|^2 (+inf for the pad of the last tile, whose score
@@ -60,7 +52,7 @@ __global__ void __launch_bounds__(256) kmeans_prep_k(int d, int k, int T, int S4
       if (col + 4 < d) b = *(const f32x4*)(p + 4);
     }
     bf16x8 pl[3];
-    split8(a, b, pl);
+    splitbf::split8(a, b, pl);
 #pragma unroll
     for (int q = 0; q < 3; ++q) planes[((int64_t)q * nfrag + u) * 64 + lane] = __builtin_bit_cast(u32x4, pl[q]);
     return;
@@ -78,8 +70,6 @@ __global__ void zero_i32_k(int n, int32_t* p) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = 0;
 }
-
-__device__ __forceinline__ int colof(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // the tail both assignment kernels share: 128 (fused) or 4 (row kernel) rows of a workgroup -> counts and the block's partial objective
 template <int ROWS>
@@ -132,9 +122,9 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
     int tt[KT];                                                         // tiles behind the last repeat it (their scores are not looked at)
 #pragma unroll
     for (int t = 0; t < KT; ++t) tt[t] = min(tb + t, T - 1);
-    auto frag = [&](int s, int t, int q) { return planes[(q * nfrag + (int64_t)s * T + tt[t]) * 64 + lane]; };
+    auto frag = [&](int s, int t, int q) { return __builtin_bit_cast(bf16x8, planes[(q * nfrag + (int64_t)s * T + tt[t]) * 64 + lane]); };
     constexpr int NB = 4, STEPS = 4 * KT;                               // a ring of centroid fragments, three (slab, tile) steps ahead of the products
-    u32x4 kf[NB][3];
+    bf16x8 kf[NB][3];
 #pragma unroll
     for (int st = 0; st < NB - 1; ++st)
 #pragma unroll
@@ -149,7 +139,7 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
 #pragma unroll
       for (int sl = 0; sl < 4; ++sl) {
         bf16x8 xb[3];
-        split8(xr[2 * sl], xr[2 * sl + 1], xb);
+        splitbf::split8(xr[2 * sl], xr[2 * sl + 1], xb);
 #pragma unroll
         for (int e = 0; e < 4; ++e) ss = __builtin_fmaf(xr[2 * sl][e], xr[2 * sl][e], ss);
 #pragma unroll
@@ -160,9 +150,7 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
 #pragma unroll
           for (int q = 0; q < 3; ++q)
             kf[nx % NB][q] = nx < STEPS ? frag(4 * ch + nx / KT, nx % KT, q) : frag(4 * chn + (nx - STEPS) / KT, (nx - STEPS) % KT, q);
-#define SSV_MM(P, Q_) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[st % NB][P]), xb[Q_], acc[t], 0, 0, 0)
-          SSV_MM(2, 0); SSV_MM(0, 2); SSV_MM(1, 1); SSV_MM(1, 0); SSV_MM(0, 1); SSV_MM(0, 0);          // smallest terms first
-#undef SSV_MM
+          splitbf::mma6_32(acc[t], kf[st % NB], xb);
         }
       }
 #pragma unroll
@@ -187,11 +175,7 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
       }
     }
   }
-  {
-    const float ob = __shfl_xor(best, 32, 64);
-    const int oi = __shfl_xor(bi, 32, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
+  SSV_ARGMAX_FIRST_STEP(best, bi, 32);                                     // the row's other half
   const float dd = fmaxf(0.f, __builtin_fmaf(-2.f, best, xx));
   const bool owner = half == 0 && row < n;
   if (owner) { labels[row] = bi; dist[row] = dd; }
@@ -218,12 +202,7 @@ __global__ void __launch_bounds__(256) kmeans_rowarg_k(const float* __restrict__
     const float sc = s[j] - hc[j];
     if (sc > best) { best = sc; bi = j; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
+  SSV_WAVE_ARGMAX_FIRST(best, bi);
   const float* xp = x + (int64_t)(row0 + rr) * d;
   float ss = 0.f;
   for (int e = lane * 4; e < d; e += 256) {
@@ -244,7 +223,7 @@ __global__ void __launch_bounds__(256) kmeans_objective_k(int np, const float* _
   for (int i = threadIdx.x; i < np; i += 256) a += (double)partial[i];
   sm[threadIdx.x] = a;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) *objective = (float)sm[0];
 }
 
@@ -286,23 +265,17 @@ int64_t update_chunk_rows(int64_t n, int d, int kp) {                           
   if (r > n) r = n;
   return r < 1 ? 1 : r;
 }
-ssv_conv_desc gemm_desc(int rows, int C, int K, int arithmetic) {
-  ssv_conv_desc cd = {};
-  cd.arithmetic = arithmetic;
-  cd.N = rows; cd.H = 1; cd.W = 1; cd.C = C; cd.K = K; cd.R = 1; cd.S = 1; cd.stride = 1; cd.pad = 0; cd.Ho = 1; cd.Wo = 1;
-  return cd;
-}
 bool shape_ok(int64_t n, int32_t d, int32_t k) { return n >= 1 && n <= (1ll << 30) && d >= 1 && d <= MAX_D && k >= 1 && k <= MAX_K && k <= n; }
 size_t assign_ws(int64_t n, int d, int k, int arithmetic) {
-  size_t b = (((size_t)cdiv64(n, 4) * 4) + 255) & ~(size_t)255;                       // the partial objectives of either route
+  size_t b = up256((size_t)cdiv64(n, 4) * 4);                      // the partial objectives of either route
   if (arithmetic != SSV_ARITH_BF16X3) b += (size_t)assign_chunk_rows(n) * k * 4 + 256;
   return b;
 }
 size_t update_ws(int64_t n, int d, int k, int arithmetic, size_t* sums_bytes, size_t* oh_bytes) {
   const int kp = (k + 3) & ~3;
   const int64_t cr = update_chunk_rows(n, d, kp);
-  const size_t sb = (((size_t)kp * d * 4) + 255) & ~(size_t)255, ob = (((size_t)cr * kp * 4) + 255) & ~(size_t)255;
-  ssv_conv_desc a = gemm_desc((int)cr, d, kp, arithmetic), b = gemm_desc((int)(n % cr ? n % cr : cr), d, kp, arithmetic);
+  const size_t sb = up256((size_t)kp * d * 4), ob = up256((size_t)cr * kp * 4);
+  ssv_conv_desc a = gemm_conv_desc((int)cr, d, kp, arithmetic), b = gemm_conv_desc((int)(n % cr ? n % cr : cr), d, kp, arithmetic);
   const size_t wa = ssv_conv2d_wgrad_workspace_bytes(&a), wb = ssv_conv2d_wgrad_workspace_bytes(&b);
   if (sums_bytes) *sums_bytes = sb;
   if (oh_bytes) *oh_bytes = ob;
@@ -363,12 +336,12 @@ extern "C" int ssv_kmeans_assign(int64_t n, int32_t d, int32_t k, const float* x
 #undef SSV_KM
     SSV_CHECK_LAUNCH("kmeans_fused_k");
   } else {
-    float* S = (float*)((char*)ws + ((((size_t)cdiv64(n, 4) * 4) + 255) & ~(size_t)255));
+    float* S = (float*)((char*)ws + up256((size_t)cdiv64(n, 4) * 4));
     const int64_t cr = assign_chunk_rows(n);
     np = (int)cdiv64(n, 4);
     for (int64_t r0 = 0; r0 < n; r0 += cr) {
       const int rows = (int)(n - r0 < cr ? n - r0 : cr);
-      ssv_conv_desc cd = gemm_desc(rows, d, k, SSV_ARITH_F32_MFMA);
+      ssv_conv_desc cd = gemm_conv_desc(rows, d, k, SSV_ARITH_F32_MFMA);
       if (int rc = ssv_conv2d_fwd(&cd, x + r0 * d, centroids, nullptr, nullptr, S, stream)) return rc;         // S[rows, k] = X[r0 : r0 + rows] C^T
       ProfScope ps(SSV_PROF_MISC, s);
       hipLaunchKernelGGL(kmeans_rowarg_k, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, (const float*)S, rows, (int)r0, d, k, x, hc, labels, dist, counts, partial);
@@ -405,7 +378,7 @@ extern "C" int ssv_kmeans_update(int64_t n, int32_t d, int32_t k, const float* x
       hipLaunchKernelGGL(kmeans_onehot_k, dim3((unsigned)cdiv64(total4, 256)), dim3(256), 0, s, total4, kp / 4, labels + r0, (f32x4*)oh);
       SSV_CHECK_LAUNCH("kmeans_onehot_k");
     }
-    ssv_conv_desc cd = gemm_desc(rows, d, kp, arithmetic);
+    ssv_conv_desc cd = gemm_conv_desc(rows, d, kp, arithmetic);
     if (int rc = ssv_conv2d_wgrad(&cd, x + r0 * d, oh, sums, r0 > 0, gws, ws_bytes - sb - ob, stream)) return rc;   // sums[kp, d] (+)= onehot^T X, chunks in row order
   }
   {

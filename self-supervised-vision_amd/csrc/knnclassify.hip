@@ -272,8 +272,6 @@ __global__ void __launch_bounds__(256) knn_vote_k(int k, int64_t n, int C, int t
 // ---- the partition of one search ------------------------------------------------------------------------------------------------------------------------------------
 struct Plan { int cr, pc, arith; size_t s_bytes, planes_bytes, tmp_bytes; };
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // false (with the reason in `why`, if given) for what ssv_knn_search refuses
 bool make_plan(int64_t m, int64_t n, int32_t d, int32_t k, int32_t arithmetic, int32_t chunk_rows, int32_t part_cols, Plan* p, const char** why) {
   const char* dummy;
@@ -339,9 +337,7 @@ extern "C" int ssv_knn_search(int64_t m, int64_t n, int32_t d, int32_t k, const 
       if (int rc = ssv_split_planes((int64_t)cols * d, bank + c0 * d, planes, stream)) return rc;
     for (int64_t r0 = 0; r0 < m; r0 += p.cr) {
       const int rows = (int)(m - r0 < p.cr ? m - r0 : p.cr);
-      ssv_conv_desc cd = {};
-      cd.arithmetic = p.arith; cd.w_planes = planes;
-      cd.N = rows; cd.H = 1; cd.W = 1; cd.C = d; cd.K = cols; cd.R = 1; cd.S = 1; cd.stride = 1; cd.pad = 0; cd.Ho = 1; cd.Wo = 1;
+      ssv_conv_desc cd = gemm_conv_desc(rows, d, cols, p.arith, planes);
       if (int rc = ssv_conv2d_fwd(&cd, queries + r0 * d, bank + c0 * d, nullptr, nullptr, S, stream)) return rc;      // S[rows, cols] = Q[r0 : r0 + rows] B[c0 : c0 + cols]^T
       ProfScope ps(SSV_PROF_MISC, s);
       float* osim = c0 == 0 ? sim + r0 * k : tsim;

@@ -248,7 +248,7 @@ ntxent_loss_k(int rows, const float* __restrict__ lse, const float* __restrict__
   for (int i = threadIdx.x; i < rows; i += 256) s += (double)lse[i] - (double)pos[i];
   sm[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) *loss = (float)(sm[0] * (double)scale);
 }
 
@@ -266,7 +266,7 @@ mse_pair_k(int64_t n, const float* __restrict__ o1, const float* __restrict__ o2
   }
   sm[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
 }
 __global__ void sum_partials_k(int nblk, const double* __restrict__ part, float scale, float* __restrict__ out) {
@@ -295,7 +295,7 @@ barlow_cgrad_k(int D, const float* __restrict__ craw, float inv_b, float lambda,
   }
   sm[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
 }
 

@@ -165,7 +165,7 @@ __global__ void pirl_loss_sum_k(int B, const double* __restrict__ rowloss, float
   for (int i = threadIdx.x; i < B; i += 256) s += rowloss[i];
   sm[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) *loss = (float)(sm[0] / (double)B);
 }
 

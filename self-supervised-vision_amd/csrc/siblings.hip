@@ -18,7 +18,7 @@ negdot_pair_k(int64_t n, const float* __restrict__ o1, const float* __restrict__
   }
   sm[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
 }
 __global__ void finish_sum_k(int nblk, const double* __restrict__ part, float scale, float* __restrict__ out, int accumulate) {
@@ -123,7 +123,7 @@ __global__ void moco_loss_sum_k(int N, const double* __restrict__ part, float* _
   for (int i = threadIdx.x; i < N; i += 256) s += part[i];
   sm[threadIdx.x] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+  SSV_BLOCK_SUM_256(sm);
   if (threadIdx.x == 0) *loss = (float)(sm[0] / (double)N);
 }
 

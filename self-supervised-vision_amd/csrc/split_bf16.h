@@ -133,4 +133,25 @@ __device__ __forceinline__ void mma6x2(f32x4& acc, f32x4& lo, const bf16x8 (&col
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(col[0], row[0], acc, 0, 0, 0);
 }
 
+// ---- the same arithmetic on v_mfma_f32_32x32x16_bf16 (attention forward, the fused kNN search, the fused k-means assignment) --------------------------------
+// One instruction contracts a 16-wide slab: lane l supplies row (l & 31) of its operand, k = 8 (l >> 5) .. + 7 - eight consecutive floats of a row, which
+// split8 turns into the three planes' fragments in registers.
+__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8 (&pl)[3]) {
+  u32x2 pa[3], pb[3];
+  split4(a, pa);
+  split4(b, pb);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) pl[q] = __builtin_bit_cast(bf16x8, u32x4{pa[q][0], pa[q][1], pb[q][0], pb[q][1]});
+}
+// mma6 on the 32 x 32 accumulator: the same six terms in the same order, smallest first - the order IS the arithmetic's contract, so no kernel restates it.
+// `a` is the instruction's A operand (keys, columns of the Gram matrix, centroids), `b` its B operand (the queries / rows, whose index stays on the lane).
+__device__ __forceinline__ void mma6_32(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
+#define SSV_MM(P, Q) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[P], b[Q], acc, 0, 0, 0)
+  SSV_MM(2, 0); SSV_MM(0, 2); SSV_MM(1, 1); SSV_MM(1, 0); SSV_MM(0, 1); SSV_MM(0, 0);
+#undef SSV_MM
+}
+// Element j (0..15) of a 32 x 32 accumulator in lane l belongs to B-operand row (l & 31) - one lane, one query - and to THIS row of the A operand
+// (half = l >> 5): the key / column / centroid within the tile.  The fp32 form (v_mfma_f32_32x32x2_f32) has the same map.
+__device__ __forceinline__ int acc32_row(int j, int half) { return (j & 3) + 8 * (j >> 2) + 4 * half; }
+
 }  // namespace splitbf

@@ -27,7 +27,7 @@ __device__ __forceinline__ f32x16 zero16() {
   for (int i = 0; i < 16; ++i) z[i] = 0.f;
   return z;
 }
-__device__ __forceinline__ int rowof(int j, int half) { return (j & 3) + 8 * (j >> 2) + 4 * half; }
+using splitbf::acc32_row;
 
 // 32 consecutive floats of one row -> registers (optionally scaled)
 __device__ __forceinline__ void load_row32(const float* __restrict__ p, float* __restrict__ r, float scale) {
@@ -157,7 +157,7 @@ attn_fwd_k(int T, int heads, const float* __restrict__ Q, const float* __restric
       float mt = -INFINITY;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (k0 + rowof(j, half) >= T) s[j] = -INFINITY;
+        if (k0 + acc32_row(j, half) >= T) s[j] = -INFINITY;
         mt = fmaxf(mt, s[j]);
       }
       mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
@@ -173,8 +173,8 @@ attn_fwd_k(int T, int heads, const float* __restrict__ Q, const float* __restric
       for (int j = 0; j < 16; ++j) { o_lo[j] *= alpha; o_hi[j] *= alpha; }
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (k0 + rowof(j, 0) >= T) continue;                   // both keys of this step are padding (wave-uniform): P is 0 there
-        const float* vr = sv[buf] + rowof(j, half) * TS;
+        if (k0 + acc32_row(j, 0) >= T) continue;                   // both keys of this step are padding (wave-uniform): P is 0 there
+        const float* vr = sv[buf] + acc32_row(j, half) * TS;
         o_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[c], s[j], o_lo, 0, 0, 0);
         o_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32 + c], s[j], o_hi, 0, 0, 0);
       }
@@ -202,15 +202,6 @@ constexpr int KVP = 32 * 128;                                // bytes of one [32
 __device__ __forceinline__ int kplane_off(int key, int chunk) { return key * 128 + ((chunk ^ ((key >> 1) & 7)) << 4); }      // ds_read_b128 of lanes = keys: 8 distinct chunks per key parity
 __device__ __forceinline__ int vplane_off(int key, int chunk) { return key * 128 + ((chunk ^ (((key >> 1) & 1) << 2)) << 4); } // transposed reads: keys q and q + 2 on opposite 64-byte halves
 
-// eight floats -> the three planes' bf16x8
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8 (&pl)[3]) {
-  u32x2 pa[3], pb[3];
-  splitbf::split4(a, pa);
-  splitbf::split4(b, pb);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) pl[q] = __builtin_bit_cast(bf16x8, u32x4{pa[q][0], pa[q][1], pb[q][0], pb[q][1]});
-}
-
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, 2)
 attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ld, float scale,
@@ -228,7 +219,7 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
     const float* qp = Q + (tok0 + qrow) * ld + h * DH + 8 * half;
     const float sc = scale * LOG2E;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) split8(*(const f32x4*)(qp + 16 * s) * sc, *(const f32x4*)(qp + 16 * s + 4) * sc, qf[s]);
+    for (int s = 0; s < 4; ++s) splitbf::split8(*(const f32x4*)(qp + 16 * s) * sc, *(const f32x4*)(qp + 16 * s + 4) * sc, qf[s]);
   }
   f32x16 o_lo = zero16(), o_hi = zero16();
   float m = -INFINITY, l = 0.f;
@@ -275,14 +266,12 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
         bf16x8 kf[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) kf[q] = *(const bf16x8*)(kp + q * KVP + kplane_off(c, 2 * sl + half));
-#define SSV_MM(P, Q_) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[P], qf[sl][Q_], s, 0, 0, 0)
-        SSV_MM(2, 0); SSV_MM(0, 2); SSV_MM(1, 1); SSV_MM(1, 0); SSV_MM(0, 1); SSV_MM(0, 0);
-#undef SSV_MM
+        splitbf::mma6_32(s, kf, qf[sl]);
       }
       float mt = -INFINITY;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (k0 + rowof(j, half) >= T) s[j] = -INFINITY;
+        if (k0 + acc32_row(j, half) >= T) s[j] = -INFINITY;
         mt = fmaxf(mt, s[j]);
       }
       mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
@@ -303,7 +292,7 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
       for (int sp = 0; sp < 2; ++sp) {
         if (k0 + 16 * sp >= T) continue;                       // every key of this slab is padding (uniform): P is 0 there
         bf16x8 pf[3];
-        split8(f32x4{s[8 * sp], s[8 * sp + 1], s[8 * sp + 2], s[8 * sp + 3]}, f32x4{s[8 * sp + 4], s[8 * sp + 5], s[8 * sp + 6], s[8 * sp + 7]}, pf);
+        splitbf::split8(f32x4{s[8 * sp], s[8 * sp + 1], s[8 * sp + 2], s[8 * sp + 3]}, f32x4{s[8 * sp + 4], s[8 * sp + 5], s[8 * sp + 6], s[8 * sp + 7]}, pf);
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           bf16x8 vf[3];
@@ -316,10 +305,7 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
             typedef short s16x8 __attribute__((ext_vector_type(8)));
             vf[q] = __builtin_bit_cast(bf16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
           }
-          f32x16& o = hh ? o_hi : o_lo;
-#define SSV_MM(P, Q_) o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[P], pf[Q_], o, 0, 0, 0)
-          SSV_MM(2, 0); SSV_MM(0, 2); SSV_MM(1, 1); SSV_MM(1, 0); SSV_MM(0, 1); SSV_MM(0, 0);
-#undef SSV_MM
+          splitbf::mma6_32(hh ? o_hi : o_lo, vf, pf);
         }
       }
     }
@@ -383,13 +369,13 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_dq_k(int T, int heads, const
       for (int i = 0; i < 32; ++i) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(kreg[i], doreg[i], dp, 0, 0, 0);
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        const float p = (k0 + rowof(j, half) < T) ? ex2(s[j] - lse) : 0.f;
+        const float p = (k0 + acc32_row(j, half) < T) ? ex2(s[j] - lse) : 0.f;
         s[j] = p * (dp[j] - delta);                            // dS^T
       }
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (k0 + rowof(j, 0) >= T) continue;                   // padding keys: dS is 0
-        const float* kr = sk[buf] + rowof(j, half) * TS;
+        if (k0 + acc32_row(j, 0) >= T) continue;                   // padding keys: dS is 0
+        const float* kr = sk[buf] + acc32_row(j, half) * TS;
         g_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[c], s[j], g_lo, 0, 0, 0);
         g_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32 + c], s[j], g_hi, 0, 0, 0);
       }
@@ -445,16 +431,16 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
       for (int i = 0; i < 32; ++i) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(qreg[i], vreg[i], dp, 0, 0, 0);
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        const int r = rowof(j, half);
+        const int r = acc32_row(j, half);
         const float p = (q0 + r < T && kvalid) ? ex2(s[j] - sstat[buf][0][r]) : 0.f;
         s[j] = p;                                              // P
         dp[j] = p * (dp[j] - sstat[buf][1][r]);                // dS
       }
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (q0 + rowof(j, 0) >= T) continue;                   // padding queries: P and dS are 0
-        const float* qr = sq[buf] + rowof(j, half) * TS;
-        const float* dr = sd[buf] + rowof(j, half) * TS;
+        if (q0 + acc32_row(j, 0) >= T) continue;                   // padding queries: P and dS are 0
+        const float* qr = sq[buf] + acc32_row(j, half) * TS;
+        const float* dr = sd[buf] + acc32_row(j, half) * TS;
         dv_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[c], s[j], dv_lo, 0, 0, 0);
         dv_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[32 + c], s[j], dv_hi, 0, 0, 0);
         dk_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[c], dp[j], dk_lo, 0, 0, 0);
@@ -578,7 +564,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
         const f32x4 l4 = *(const f32x4*)&sstat[0][8 * jj + 4 * half], d4 = *(const f32x4*)&sstat[1][8 * jj + 4 * half];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int j = 4 * jj + e, r = rowof(j, half);
+          const int j = 4 * jj + e, r = acc32_row(j, half);
           const float p = (q0 + r < T && kvalid) ? ex2(s[j] - l4[e]) : 0.f;
           s[j] = p;                                            // P
           dp[j] = p * (dp[j] - d4[e]);                         // dS
@@ -586,9 +572,9 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       }
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (q0 + rowof(j, 0) >= T) continue;                   // padding queries: P and dS are 0
-        const float* qr = sq + rowof(j, half) * TS;
-        const float* dr = sd + rowof(j, half) * TS;
+        if (q0 + acc32_row(j, 0) >= T) continue;                   // padding queries: P and dS are 0
+        const float* qr = sq + acc32_row(j, half) * TS;
+        const float* dr = sd + acc32_row(j, half) * TS;
         dv_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[c], s[j], dv_lo, 0, 0, 0);
         dv_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[32 + c], s[j], dv_hi, 0, 0, 0);
         dk_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[c], dp[j], dk_lo, 0, 0, 0);
@@ -596,7 +582,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       }
       // dS (query on the register index, key on the lane) -> dS^T (key on the register index, query on the lane) through this wave's scratch
 #pragma unroll
-      for (int j = 0; j < 16; ++j) myscr[rowof(j, half) * 36 + c] = dp[j];
+      for (int j = 0; j < 16; ++j) myscr[acc32_row(j, half) * 36 + c] = dp[j];
       f32x16 st_;
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
@@ -606,8 +592,8 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       f32x16 g_lo = zero16(), g_hi = zero16();
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if (k0 + rowof(j, 0) >= T) continue;                   // both keys of this step are padding (wave-uniform): dS is 0 there
-        const float* kr = sK + (k0 + rowof(j, half)) * TS;
+        if (k0 + acc32_row(j, 0) >= T) continue;                   // both keys of this step are padding (wave-uniform): dS is 0 there
+        const float* kr = sK + (k0 + acc32_row(j, half)) * TS;
         g_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[c], st_[j], g_lo, 0, 0, 0);
         g_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32 + c], st_[j], g_hi, 0, 0, 0);
       }

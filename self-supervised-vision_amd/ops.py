@@ -789,6 +789,11 @@ def barlow_cgrad(craw, inv_b, lmbda):
     return loss, g
 
 
+def _arith_code():
+    """ARITHMETIC as the C ABI's code, for the entry points that take it as an argument (the searches and k-means)"""
+    return _lib.ARITH_BF16X3 if ARITHMETIC == "bf16x3" else _lib.ARITH_F32_MFMA
+
+
 def knn_label_agreement(z, labels, k):
     """Number of (query, neighbour) pairs with equal labels among each row's k nearest neighbours by inner product
     (best hit dropped), as a python int.  z [n,d] fp32 device, labels [n] int32 device."""
@@ -799,17 +804,13 @@ def knn_label_agreement(z, labels, k):
         d = z.shape[1]
     z = z.contiguous()
     count = torch.empty((1,), dtype=torch.int64, device=z.device)
-    arith = _lib.ARITH_BF16X3 if ARITHMETIC == "bf16x3" else _lib.ARITH_F32_MFMA
+    arith = _arith_code()
     ws = torch.empty(_lib.load().ssv_knn_workspace_bytes_arith(n, d, arith), dtype=torch.uint8, device=z.device)    # up to ~1 GB: not kept in the training scratch
     call("ssv_knn_label_agreement_arith", n, d, ptr(z), ptr(labels), int(k), ptr(count), arith, ptr(ws), ws.numel(), stream())
     return int(count.item())
 
 
 # ------------------------------------------------------------------------------------------- k-means / cluster accuracy (csrc/kmeans.hip)
-def _kmeans_arith():
-    return _lib.ARITH_BF16X3 if ARITHMETIC == "bf16x3" else _lib.ARITH_F32_MFMA
-
-
 def _kmeans_operands(who, x, centroids):
     """Checks shared by the two k-means calls; returns (x, centroids, n, d, k, dp) with dp the column count the kernels see (d rounded up to 4)."""
     _lib._dev(x, centroids)
@@ -850,7 +851,7 @@ def kmeans_assign(x, centroids, prep=None, prep_ready=False):
     dist = torch.empty(n, dtype=torch.float32, device=x.device)
     counts = torch.empty(k, dtype=torch.int32, device=x.device)
     objective = torch.empty((), dtype=torch.float32, device=x.device)
-    arith = _kmeans_arith()
+    arith = _arith_code()
     ws = workspace.get(lib.ssv_kmeans_workspace_bytes(n, dp, k, arith), x.device)
     call("ssv_kmeans_assign", n, dp, k, ptr(xp), ptr(cp), ptr(prep), int(bool(prep_ready)), ptr(labels), ptr(dist), ptr(counts), ptr(objective), arith,
          ptr(ws), ws.numel(), stream())
@@ -866,7 +867,7 @@ def kmeans_update(x, labels, counts, centroids, prep=None):
         raise _lib.SsvError(f"kmeans_update: contiguous int32 labels [{n}] and counts [{k}] expected")
     xp, cp = _pad4(x, dp), _pad4(centroids, dp)
     lib = _lib.load()
-    arith = _kmeans_arith()
+    arith = _arith_code()
     ws = workspace.get(lib.ssv_kmeans_workspace_bytes(n, dp, k, arith), x.device)
     call("ssv_kmeans_update", n, dp, k, ptr(xp), ptr(labels), ptr(counts), ptr(cp), ptr(prep), arith, ptr(ws), ws.numel(), stream())
     if cp is not centroids:
@@ -907,7 +908,7 @@ def knn_search(queries, bank, k, chunk_rows=0, part_cols=0):
         raise _lib.SsvError(f"knn_search: need m >= 1 and 1 <= k <= min(n, {_lib.KNN_MAX_K}) (got m = {m}, n = {n}, k = {k})")
     dp = (d + 3) // 4 * 4
     qp, bp = _pad4(queries, dp), _pad4(bank, dp)
-    arith = _kmeans_arith()
+    arith = _arith_code()
     need = _lib.load().ssv_knn_search_workspace_bytes(m, n, dp, k, arith, int(chunk_rows), int(part_cols))
     ws = workspace.get(max(need, 16), queries.device)                   # need == 0: a partition the library refuses - the call below says why
     sim = torch.empty((m, k), dtype=torch.float32, device=queries.device)

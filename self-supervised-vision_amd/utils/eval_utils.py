@@ -16,13 +16,10 @@ from .. import ops
 
 def compute_neighbor_accuracy(fvecs, targets, k=20, device=None):
     """fvecs [n,d] and targets [n]: numpy arrays (what build_features returns) or tensors already on the GPU."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("compute_neighbor_accuracy runs on the GPU (libssv_hip); no HIP device is visible and there is no CPU fallback")
-    device = device or torch.device("cuda", torch.cuda.current_device())
-    z = torch.as_tensor(fvecs, dtype=torch.float32).to(device)
+    z, device = _features_on_device(fvecs, device, "compute_neighbor_accuracy")
     labels = torch.as_tensor(targets).to(device=device, dtype=torch.int32).contiguous()
     n = z.shape[0]
-    if z.dim() != 2 or labels.shape != (n,):
+    if labels.shape != (n,):
         raise ValueError(f"expected fvecs [n,d] and targets [n], got {tuple(z.shape)} and {tuple(labels.shape)}")
     k = min(int(k), n - 1)                                          # tiny evaluation sets (synthetic smoke runs)
     return ops.knn_label_agreement(z, labels, k) / float(n * k)

@@ -114,13 +114,13 @@ def test_bench_dump_outputs_writes_loss_and_a_bounded_parameter_sample(tmp_path)
 
 
 def test_committed_counters_were_measured_on_the_current_sources():
-    """The build identity is the sha256 over the kernel sources in link order + the two headers + the compile flags (csrc/Makefile: SRC_SHA).  When the sources have moved on since the
+    """The build identity is the sha256 over the kernel sources in link order + every header they include (csrc/Makefile: HDRS) + the compile flags (csrc/Makefile: SRC_SHA).  When the sources have moved on since the
     counters under profiles/ were measured, bench.py prints `counters_stale: true` - this test then SKIPS with the reason (a reminder to re-run tools/profile_step.sh
     and tools/bench_conv.py), it does not fail: stale counters are withheld, never wrong."""
     sys.path.insert(0, ROOT)
     import bench
     csrc = os.path.join(ROOT, "self-supervised-vision_amd", "csrc")
-    # the Makefile's own recipe (sources in link order + the two headers + the compile flags): `make print-src-sha`
+    # the Makefile's own recipe (sources in link order + the headers of HDRS + the compile flags): `make print-src-sha`
     now = subprocess.run(["make", "-s", "-C", csrc, "print-src-sha"], capture_output=True, text=True, check=True).stdout.strip()
     assert len(now) == 16
     from ssv_amd import _lib
@@ -129,6 +129,32 @@ def test_committed_counters_were_measured_on_the_current_sources():
              if bench.read_committed_counters(os.path.join(ROOT, "profiles"), f)[1] != now]
     if stale:
         pytest.skip(f"counters under profiles/ were measured on another build than the current sources ({now}): {stale} - bench.py will print counters_stale")
+
+
+def test_every_included_header_is_part_of_the_build_identity():
+    """csrc/Makefile lists the project's headers once (HDRS): they are prerequisites of every object and hashed into SRC_SHA.  A header that a source (or
+    another header) includes with quotes but HDRS does not name would change the library without rebuilding it or moving ssv_source_sha16()."""
+    import re
+    csrc = os.path.join(ROOT, "self-supervised-vision_amd", "csrc")
+    listed = subprocess.run(["make", "-s", "-C", csrc, "print-hdrs"], capture_output=True, text=True, check=True).stdout.split()
+    listed = {os.path.normpath(os.path.join(csrc, h)) for h in listed}
+    assert listed and all(os.path.isfile(h) for h in listed), listed
+    todo = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    assert any(p.endswith(".hip") for p in todo)
+    seen, included = set(), {}
+    while todo:
+        path = todo.pop()
+        if path in seen:
+            continue
+        seen.add(path)
+        with open(path) as fh:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fh.read(), re.M):
+                hdr = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+                assert os.path.isfile(hdr), f"{path} includes {inc}, which does not exist"
+                included.setdefault(hdr, path)
+                todo.append(hdr)
+    missing = {os.path.relpath(h, csrc): os.path.relpath(by, csrc) for h, by in included.items() if h not in listed}
+    assert not missing, f"included but not in csrc/Makefile's HDRS (header: first includer): {missing}"
 
 
 def test_a_stopped_parent_takes_its_ranks_with_it(tmp_path):
