@@ -416,6 +416,39 @@ int ssv_scale(int64_t n, float* x, const float* factor_dev, void* stream);
 int ssv_barlow_cgrad(int32_t D, const float* craw, float inv_b, float lambda, float* loss, float* G,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- VICReg loss (Bardes, Ponce, LeCun 2022; csrc/vicreg.hip): the element-wise work around its GEMMs.  The reference has no such loss.
+ * For embeddings x, y [B][D] fp32, dense:
+ *     sim = mean over B*D of (x - y)^2;   xc = x - mean_b(x);   s_x[j] = sqrt(var_unbiased(x[:, j]) + eps);   C_x = xc^T xc / (B - 1)   (y likewise)
+ *     std = mean_j relu(1 - s_x[j]) / 2 + mean_j relu(1 - s_y[j]) / 2;   cov = sum_{i != j} C_x[i][j]^2 / D + sum_{i != j} C_y[i][j]^2 / D
+ *     loss = sim_coeff sim + std_coeff std + cov_coeff cov
+ *     dx = 2 sim_coeff (x - y) / (B D)  -  std_coeff / (2 D (B - 1)) xc[:, j] / s_x[j] where s_x[j] < 1  +  4 cov_coeff / (D (B - 1)) xc offdiag(C_x)
+ * (dy mirrors it).  The terms in xc have zero column mean, so the backward of the centring is the identity and no kernel applies one.
+ * The sequence is ssv_vicreg_prep -> craw[v] = xc[v]^T xc[v] by the weight-gradient GEMM (ssv_conv2d_wgrad) -> ssv_vicreg_cgrad -> d[v] = xc[v] G[v] + e[v] by
+ * the forward GEMM with e as its addend (ssv_conv2d_fwd; G is symmetric).
+ *
+ * ssv_vicreg_prep: one workgroup per strip of 32 columns (128-byte row segments, 16 bytes per lane) walks the rows three times: column sums -> means; centred
+ *   values written with their squares summed -> s; the hinge term added where it is active.  x and y are read twice each.  The variance is formed from the
+ *   centred values.  Column sums run in double, in a fixed order; no floating-point atomics: equal inputs give equal bits.
+ *   xc [2][B][D]   xc[0] = x - mean, xc[1] = y - mean: the layout a batch-2 GEMM takes
+ *   s  [2][D]      s_x then s_y
+ *   e  [2][B][D]   the sim and std terms of dx, then of dy.  Where the hinge is inactive (s >= 1, or std_coeff == 0) e is the sim term alone, bit for bit
+ *                  g (x - y) with g = (float)(2 sim_coeff / (B D)) for x and its exact negation for y
+ *   parts [2]      sim_coeff sim, std_coeff std
+ *   cov_coeff is not used by the launch: it is checked here so that a bad configuration is refused before the first kernel of the sequence.
+ * ssv_vicreg_cgrad: craw [2][D][D] as the GEMM left it; overwritten IN PLACE by G = 4 cov_coeff / (D (B - 1)^2) craw with an exactly zero diagonal (one fp32
+ *   multiply per element: G is symmetric bit for bit wherever craw is).  loss [4] = total, then the weighted sim, std, cov terms (sim and std copied from
+ *   `parts`); total = (sim + std) + cov in fp32.  The D x D reduction goes through `ws` in a fixed order, in double.
+ * Limits, both calls: 2 <= B, D % 32 == 0, 32 <= D <= SSV_KNN_MAX_D (8192), B * D <= 2^30; the three coefficients finite and >= 0; eps finite and >= 0; no NULL
+ *   pointer; x, y, xc, e, craw and ws 16-byte aligned; ws_bytes >= ssv_vicreg_workspace_bytes(B, D), which is 0 for a shape that is refused.  Anything else
+ *   returns SSV_ERR_INVALID (a short workspace too) with a message before anything is launched or written; nothing is clamped.  Outputs alias no input.
+ * Not built: the gathered (data-parallel) loss, a product that computes one triangle of C only, the off-diagonal sum in the GEMM's epilogue.
+ * The ABI version stays 124: entry points were only added. */
+size_t ssv_vicreg_workspace_bytes(int32_t B, int32_t D);
+int ssv_vicreg_prep(int32_t B, int32_t D, const float* x, const float* y, float sim_coeff, float std_coeff, float cov_coeff, float eps,
+                    float* xc /*[2][B][D]*/, float* s /*[2][D]*/, float* e /*[2][B][D]*/, float* parts /*[2]*/, void* ws, size_t ws_bytes, void* stream);
+int ssv_vicreg_cgrad(int32_t B, int32_t D, float* craw /*[2][D][D], in place*/, float cov_coeff, const float* parts /*[2]*/, float* loss /*[4]*/,
+                     void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimizer: optim.SGD(momentum=0.9, nesterov=True, weight_decay) utils/train_utils.py:11-13
  * over a flat arena of n floats.  first_step != 0 seeds buf = g.  g2 (may be NULL) is a second gradient slab that is
  * added to g first: the two views' backward passes run on two HIP streams and accumulate into separate slabs. */

@@ -23,6 +23,7 @@ ARITH_F32_MFMA, ARITH_BF16X3 = 0, 6      # ssv_conv_desc.arithmetic (include/ssv
 BLUR_MAX_PIXELS, BLUR_MAX_SIGMA = 81920, 1000.0      # SSV_BLUR_MAX_PIXELS, SSV_BLUR_MAX_SIGMA (include/ssv_hip.h)
 KMEANS_MAX_K, KMEANS_MAX_D = 4096, 8192              # SSV_KMEANS_MAX_K, SSV_KMEANS_MAX_D (include/ssv_hip.h)
 KNN_MAX_K, KNN_MAX_D, KNN_MAX_CLASSES, KNN_MAX_TOPN = 1024, 8192, 4096, 8      # SSV_KNN_MAX_* (include/ssv_hip.h)
+VICREG_MAX_D = KNN_MAX_D                             # the VICReg entry points share SSV_KNN_MAX_D (include/ssv_hip.h)
 
 
 class ConvDesc(C.Structure):
@@ -144,6 +145,9 @@ SIGNATURES = {
     "ssv_mse_pair_fwd_bwd": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssv_scale": (C.c_int, [_i64, _vp, _vp, _vp]),
     "ssv_barlow_cgrad": (C.c_int, [_i32, _vp, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "ssv_vicreg_workspace_bytes": (_sz, [_i32, _i32]),
+    "ssv_vicreg_prep": (C.c_int, [_i32, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ssv_vicreg_cgrad": (C.c_int, [_i32, _i32, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
     "ssv_sgd_nesterov": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, C.c_int, _vp]),
     "ssv_sgd_nesterov_dev": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ssv_lars_chunk_floats": (_i64, []),

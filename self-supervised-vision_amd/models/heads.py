@@ -3,6 +3,7 @@ Parameter names, shapes and init draws follow the reference so state_dicts and s
   SimCLR ProjectionHead  models/simclr.py:23-36   fc1 bn1 fc2 bn2
   BYOL   MLP             models/byol.py:24-34     fc1 bn1 fc2
   Barlow ProjectionHead  models/barlow.py:23-36   layer1.{0,1} layer2.{0,1} layer3, then L2-normalise
+  VICReg ProjectionHead  (not in the reference)   Barlow's three layers without the final L2 normalisation
 """
 import math
 
@@ -64,3 +65,10 @@ class BarlowProjectionHead(hnn.HipModule):
     def _run(self, tape, x):
         x = self.layer2._run(tape, self.layer1._run(tape, x))
         return hnn.l2_normalize(tape, self.layer3._run(tape, x))
+
+
+class VicregProjectionHead(BarlowProjectionHead):
+    """VICReg's expander: the loss works on the raw embeddings (its variance term fixes their scale), so nothing is normalised."""
+
+    def _run(self, tape, x):
+        return self.layer3._run(tape, self.layer2._run(tape, self.layer1._run(tape, x)))

@@ -235,6 +235,14 @@ def _planes(w):
     return pl
 
 
+def drop_planes(t):
+    """Forget the cached bf16 planes of every operand inside ``t``'s memory: for a GEMM operand that is not a weight (it changes in place, or it dies with
+    the call that made it) - the cache would otherwise keep its planes and its storage alive until the next optimizer step."""
+    lo, hi = t.data_ptr(), t.data_ptr() + t.element_size() * t.numel()
+    for key in [k for k in _PLANES if lo <= k[0] < hi]:
+        del _PLANES[key]
+
+
 def _transposed_filter(w, wshape):
     """wt[c][R-1-r][S-1-s][k] = w[k][r][s][c].  Cached per HIP stream (the transpose is ordered on that stream) until the next
     zero_grad(); the entry keeps the weight's storage alive, so an address can never come back as a different tensor."""
@@ -787,6 +795,42 @@ def barlow_cgrad(craw, inv_b, lmbda):
     ws = _lib.workspace.get(_lib.load().ssv_reduce_workspace_bytes(d * d), craw.device)
     call("ssv_barlow_cgrad", d, ptr(craw), float(inv_b), float(lmbda), ptr(loss), ptr(g), ptr(ws), ws.numel(), stream())
     return loss, g
+
+
+# ------------------------------------------------------------------------------------------- VICReg (csrc/vicreg.hip)
+def _vicreg_ws(b, d, like):
+    nbytes = int(_lib.load().ssv_vicreg_workspace_bytes(b, d))
+    if nbytes == 0:
+        raise _lib.SsvError(f"VICReg: need B >= 2 and D a multiple of 32 in [32, {_lib.VICREG_MAX_D}] (got B={b} D={d})")
+    return workspace.get(nbytes, like.device)
+
+
+def vicreg_prep(x, y, sim_coeff, std_coeff, cov_coeff, eps):
+    """x, y [B, D] -> (xc [2, B, D] centred, s [2, D] = sqrt(unbiased variance + eps), e [2, B, D] the sim and std terms of (dx, dy),
+    parts [2] the weighted sim and std terms of the loss)."""
+    _lib._dev(x, y)
+    if x.dim() != 2 or x.shape != y.shape or not (x.is_contiguous() and y.is_contiguous()):
+        raise _lib.SsvError(f"vicreg_prep expects two dense [B, D] matrices, got {tuple(x.shape)} and {tuple(y.shape)}")
+    b, d = x.shape
+    ws = _vicreg_ws(b, d, x)
+    xc, s, e, parts = _empty((2, b, d), x), _empty((2, d), x), _empty((2, b, d), x), _empty((2,), x)
+    call("ssv_vicreg_prep", b, d, ptr(x), ptr(y), float(sim_coeff), float(std_coeff), float(cov_coeff), float(eps),
+         ptr(xc), ptr(s), ptr(e), ptr(parts), ptr(ws), ws.numel(), stream())
+    return xc, s, e, parts
+
+
+def vicreg_cgrad(craw, b, cov_coeff, parts):
+    """craw [2, D, D] = xc^T xc per view is OVERWRITTEN by G = 4 cov_coeff / (D (B-1)^2) craw with a zero diagonal; returns (loss [4] = total and the
+    weighted sim, std, cov terms, G)."""
+    _lib._dev(craw, parts)
+    if craw.dim() != 3 or craw.shape[0] != 2 or craw.shape[1] != craw.shape[2] or not craw.is_contiguous():
+        raise _lib.SsvError(f"vicreg_cgrad expects a dense [2, D, D] block, got {tuple(craw.shape)}")
+    d = craw.shape[1]
+    ws = _vicreg_ws(b, d, craw)
+    loss = _empty((4,), craw)
+    drop_planes(craw)          # craw becomes a GEMM operand after it changed in place: planes split from it before are stale
+    call("ssv_vicreg_cgrad", b, d, ptr(craw), float(cov_coeff), ptr(parts), ptr(loss), ptr(ws), ws.numel(), stream())
+    return loss, craw
 
 
 def _arith_code():

@@ -1,5 +1,5 @@
 """Loss modules of the accelerated path with the reference's constructor signatures
-(utils/losses.py:8-46 SimclrLoss, :120-142 BarlowLoss; BYOL uses nn.MSELoss, models/byol.py:89).
+(utils/losses.py:8-46 SimclrLoss, :120-142 BarlowLoss; BYOL uses nn.MSELoss, models/byol.py:89).  VicregLoss has no counterpart there.
 
 Each forward runs the fused HIP kernels (forward AND the gradient w.r.t. the embeddings), and
 returns a 0-d tensor wired into torch.autograd so ``loss.backward()`` hands dz to the heads.
@@ -192,6 +192,51 @@ class BarlowLoss(nn.Module):
         if z_i.shape != z_j.shape or z_i.dim() != 2:
             raise ValueError(f"BarlowLoss expects two [B,D] matrices, got {tuple(z_i.shape)} and {tuple(z_j.shape)}")
         return _BarlowFn.apply(z_i, z_j, self.normalize, self.lmbda)
+
+
+class _VicregFn(torch.autograd.Function):
+    """Whole VICReg loss + its gradient w.r.t. both embedding matrices, composed from the C ABI (csrc/vicreg.hip states the formulas):
+    ssv_vicreg_prep (centred views, std, the element-wise gradient part e, the sim and std terms) -> Craw[v] = xc[v]^T xc[v] (wgrad-shaped MFMA GEMM over
+    the batch) -> ssv_vicreg_cgrad (cov term, the loss, G in place over Craw) -> d[v] = xc[v] G[v] + e[v] (fwd-shaped GEMM, e as its epilogue addend; G is
+    symmetric).  The centring has no backward of its own: both terms in xc have zero column mean."""
+
+    @staticmethod
+    def forward(ctx, x, y, module):
+        b, d = x.shape
+        xc, _, e, parts = ops.vicreg_prep(x.detach().contiguous(), y.detach().contiguous(), module.sim_coeff, module.std_coeff, module.cov_coeff, module.eps)
+        craw = torch.empty((2, d, d), dtype=torch.float32, device=x.device)
+        for v in range(2):
+            ops.conv2d_wgrad(xc[v].view(b, 1, 1, d), xc[v].view(b, 1, 1, d), craw[v], craw[v], accumulate=False)      # craw[v][i][j] = sum_b xc[v][b,i] xc[v][b,j]
+        loss, g = ops.vicreg_cgrad(craw, b, module.cov_coeff, parts)
+        ctx.saved = tuple(ops.conv2d_fwd(xc[v].view(b, 1, 1, d), g[v], addend=e[v].view(b, 1, 1, d)).view(b, d) for v in range(2))
+        ops.drop_planes(g)                   # G is no weight: its bf16 planes (and craw's storage with them) must not wait in the cache for the next optimizer step
+        module.terms = loss[1:4]
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dx, dy = ctx.saved
+        g = dloss.contiguous()
+        return ops.scale_(dx, g), ops.scale_(dy, g), None
+
+
+class VicregLoss(nn.Module):
+    """VICReg (Bardes, Ponce, LeCun 2022; not in the reference): sim_coeff * invariance + std_coeff * variance hinge + cov_coeff * off-diagonal covariance
+    of two [B, D] embedding matrices, D a multiple of 32 and B >= 2.  ``terms`` holds the three weighted terms of the last forward as a device tensor."""
+
+    def __init__(self, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, eps=1e-4):
+        super().__init__()
+        self.sim_coeff, self.std_coeff, self.cov_coeff, self.eps = float(sim_coeff), float(std_coeff), float(cov_coeff), float(eps)
+        self.terms = None
+
+    def forward(self, x, y):
+        if x.dim() != 2 or y.dim() != 2 or x.shape != y.shape:
+            raise ValueError(f"VicregLoss expects two [B,D] matrices, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if x.shape[0] < 2 or x.shape[1] % 32 or x.shape[1] > _lib.VICREG_MAX_D:
+            raise ValueError(f"VicregLoss needs B >= 2 and D a multiple of 32 up to {_lib.VICREG_MAX_D}, got {tuple(x.shape)}")
+        if hdist.is_on() and hdist.world_size() > 1:
+            raise NotImplementedError("VicregLoss is single-process: the batch statistics are not gathered across ranks")
+        return _VicregFn.apply(x, y, self)
 
 
 # ------------------------------------------------------------------------------------------- sibling algorithms

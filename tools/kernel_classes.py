@@ -16,7 +16,7 @@ CLASSES = (
     ("bn_bwd", "bn_bwd"), ("bn_bwd", "bn_pool_bwd"), ("bn_bwd", "bn_sums_coarsen"),
     ("attn", "attn_"), ("norm", "ln_"),
     ("loss", "ntxent_"), ("loss", "l2norm_"), ("loss", "mse_pair_k"), ("loss", "barlow_cgrad_k"), ("loss", "sum_partials_k"), ("loss", "dino_"), ("loss", "softmax_ce_k"),
-    ("loss", "ce_reduce_k"), ("loss", "negdot_pair_k"), ("loss", "finish_sum_k"), ("loss", "relic_"), ("loss", "moco_"), ("loss", "pirl_"),
+    ("loss", "ce_reduce_k"), ("loss", "negdot_pair_k"), ("loss", "finish_sum_k"), ("loss", "relic_"), ("loss", "moco_"), ("loss", "pirl_"), ("loss", "vicreg_"),
     ("optim", "sgd_"), ("optim", "lars_"), ("optim", "adamw_k"), ("optim", "adamw_tick_k"), ("optim", "ema_k"), ("aug", "aug_"), ("aug", "multicrop"), ("aug", "center_view_k"),
     ("pool", "maxpool_"), ("pool", "gap_"),
     ("misc", "gelu_"), ("misc", "colsum_"), ("misc", "wn_fwd_k"), ("misc", "wn_bwd_k"), ("misc", "knn_agree_k"), ("misc", "knn_fused_k"), ("misc", "knn_finish_k"), ("misc", "zero_count_k"), ("misc", "scale_k"), ("misc", "add_k"),
