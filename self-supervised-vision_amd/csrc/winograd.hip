@@ -188,7 +188,7 @@ wino_output_k(int N, int H, int W, int K, int th, int tw, const float* __restric
   const int k = (blockIdx.y * 256 + lc) * 4;
   const bool kok = k < K && ts < TPP;
   const int64_t g0 = (int64_t)blockIdx.x * WG_TILES;
-  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f}, piv = {0.f, 0.f, 0.f, 0.f};
+  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
   f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {0.f, 0.f, 0.f, 0.f}, gs = {0.f, 0.f, 0.f, 0.f}, gh = {0.f, 0.f, 0.f, 0.f};
   float cnt = 0.f;
   if constexpr (MODE >= 2) { if (kok) { mu = ld4(gmean + k); is = ld4(ginvstd + k); } }
@@ -196,7 +196,9 @@ wino_output_k(int N, int H, int W, int K, int th, int tw, const float* __restric
   const size_t ps = (size_t)T * K;
   for (int p = 0; p < WG_TILES; p += TPP) {
     const int64_t t = g0 + p + ts;
-    if (!kok || t >= T) continue;
+    // K < 64: TPP > WG_TILES, and the lanes past the group's 16 tiles idle - the tiles behind them belong to the following groups, whose partials they
+    // must not enter (tests/test_gpu_wino_forms.py, lanes.lt16, holds this group by group at K = 32)
+    if (!kok || p + ts >= WG_TILES || t >= T) continue;
     const int n = (int)(t / (th * tw));
     const int r = (int)(t - (int64_t)n * th * tw);
     const int i = r / tw, j = r - i * tw;
@@ -209,6 +211,9 @@ wino_output_k(int N, int H, int W, int K, int th, int tw, const float* __restric
     f32x4 s[2][4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) { s[0][b] = m[0][b] + m[1][b] + m[2][b]; s[1][b] = m[1][b] - m[2][b] - m[3][b]; }
+    f32x4 tv[MODE == 1 ? 4 : 1], tsum = {0.f, 0.f, 0.f, 0.f};          // statistics: this tile's pixels, their sum and count
+    float tcnt = 0.f;
+    unsigned tok = 0;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const f32x4 o0 = s[a][0] + s[a][1] + s[a][2], o1 = s[a][1] - s[a][2] - s[a][3];
@@ -232,12 +237,26 @@ wino_output_k(int N, int H, int W, int K, int th, int tw, const float* __restric
           s1 += v;
           s2 += v * ((xv - mu) * is);
         }
-        if constexpr (MODE == 1) {
-          if (cnt == 0.f) piv = v;
-          const f32x4 dv = v - piv;
-          s1 += dv; s2 += dv * dv; cnt += 1.f;
-        }
+        if constexpr (MODE == 1) { tv[a * 2 + b] = v; tsum += v; tcnt += 1.f; tok |= 1u << (a * 2 + b); }
         st4(y + off, v);
+      }
+    }
+    if constexpr (MODE == 1) {
+      // the tile's (count, mean, M2) about its own mean, merged into the thread's running triple (s1 = mean, s2 = M2) as the LDS merge below merges the threads'.
+      // (A running sum about the thread's first pixel lost a digit on every channel whose first pixel was an outlier: at K = 1024, one thread per channel over 64
+      // rows, the mean sat 16x further from fp64 than a pairwise fp32 mean - tests/test_gpu_wino_forms.py, stats.g64 at lanes.one, holds the partials to 8x.)
+      const f32x4 tmean = tsum / tcnt;                                   // pixel (0, 0) of an existing tile is always inside the map: tcnt >= 1
+      f32x4 tm2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if ((tok >> q) & 1u) { const f32x4 dv = tv[q] - tmean; tm2 += dv * dv; }
+      if (cnt == 0.f) { s1 = tmean; s2 = tm2; cnt = tcnt; }
+      else {
+        const float tot = cnt + tcnt;
+        const f32x4 dlt = tmean - s1;
+        s2 += tm2 + dlt * dlt * (cnt * tcnt / tot);
+        s1 += dlt * (tcnt / tot);
+        cnt = tot;
       }
     }
   }
@@ -245,8 +264,7 @@ wino_output_k(int N, int H, int W, int K, int th, int tw, const float* __restric
   // merge the TPP partial results per channel in fixed order (thread ts == 0 of each channel lane)
   if constexpr (MODE == 1) {
     // this thread's (count, mean, M2)
-    f32x4 mean = piv, m2 = {0.f, 0.f, 0.f, 0.f};
-    if (cnt > 0.f) { mean = piv + s1 / cnt; m2 = s2 - s1 * s1 / cnt; }
+    const f32x4 mean = s1, m2 = s2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { red[0][tid * 4 + e] = mean[e]; red[1][tid * 4 + e] = m2[e]; }
     red[2][tid * 4] = cnt;

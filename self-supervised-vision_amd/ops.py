@@ -207,9 +207,9 @@ def can_fuse_conv_input(cin, cout, groups=1):
     return groups == 1 and cin % 32 == 0 and cin <= 1024 and cout % 4 == 0
 
 
-_WT_CACHE = {}          # (weight address, stream) -> (storage kept alive, transposed filter): one transpose per weight, stream and step
-_WINO_U = {}            # (weight address, stream, shape, transposed?) -> (storage kept alive, Winograd-transformed filter), same lifetime
-_PLANES = {}            # (operand address, stream, elements) -> (storage kept alive, its three bf16 planes), same lifetime
+_WT_CACHE = {}          # (weight address, stream, shape, version) -> (storage kept alive, transposed filter): one transpose per weight, stream and step
+_WINO_U = {}            # (weight address, stream, shape, transposed?, version) -> (storage kept alive, Winograd-transformed filter), same lifetime
+_PLANES = {}            # (operand address, stream, elements, version) -> (storage kept alive, its three bf16 planes), same lifetime
 
 
 def invalidate_weight_caches():
@@ -246,7 +246,9 @@ def drop_planes(t):
 def _transposed_filter(w, wshape):
     """wt[c][R-1-r][S-1-s][k] = w[k][r][s][c].  Cached per HIP stream (the transpose is ordered on that stream) until the next
     zero_grad(); the entry keeps the weight's storage alive, so an address can never come back as a different tensor."""
-    key = (w.data_ptr(), stream(), wshape)
+    # w._version, as _planes: a torch-level in-place edit of the filter (w.mul_(), w.copy_(), a foreign optimizer) must miss; the library's own raw-pointer
+    # updates call invalidate_weight_caches() (tests/test_gpu_wino_forms.py, test_cached_filters_follow_in_place_edits)
+    key = (w.data_ptr(), stream(), wshape, w._version)
     hit = _WT_CACHE.get(key)
     if hit is not None:
         return hit[1]
@@ -1335,7 +1337,7 @@ def unpad_channels(t, out, accumulate=True):
 # ------------------------------------------------------------------------------------------- Winograd F(2x2, 3x3)
 def _wino_filter(w, wshape, transposed=False):
     """U = G g G^T of the filter [K][3][3][C] - or, ``transposed``, of the rotated filter with the channel roles swapped (data gradient)."""
-    key = (w.data_ptr(), stream(), wshape, transposed)
+    key = (w.data_ptr(), stream(), wshape, transposed, w._version)      # the version as _transposed_filter: an edited filter must miss
     hit = _WINO_U.get(key)
     if hit is not None:
         return hit[1]
@@ -1493,7 +1495,7 @@ def _use_wino44(n, h, w_, c, k, max_ratio):
 
 def _wino44_filter(w, wshape, transposed=False):
     """U = G g G^T (6x6 positions) of the filter [K][3][3][C] - or, ``transposed``, of the rotated filter with the channel roles swapped (data gradient)."""
-    key = (w.data_ptr(), stream(), wshape, transposed, 44)
+    key = (w.data_ptr(), stream(), wshape, transposed, 44, w._version)      # the version as _transposed_filter: an edited filter must miss
     hit = _WINO_U.get(key)
     if hit is not None:
         return hit[1]

@@ -1,6 +1,8 @@
 """GPU: Winograd F(2x2, 3x3) (csrc/winograd.hip + the batched implicit-GEMM launches) against torch fp64 convolutions - forward with the
 fused input BatchNorm and the statistics epilogue, data gradient with the ReLU gate epilogue, weight gradient from the kept transformed
-input - and the dispatch rule that sends the deep stride-1 3x3 layers of networks/resnet.py:56-58 through it."""
+input - and the dispatch rule that sends the deep stride-1 3x3 layers of networks/resnet.py:56-58 through it.  This file runs the whole chain through
+ops.*; every transform and batched product ON ITS OWN against fp64 - narrow channel counts, ragged maps, guards, partials group by group, refusals - is
+tests/test_gpu_wino_forms.py."""
 import numpy as np
 import pytest
 import torch

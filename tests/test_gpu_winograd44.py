@@ -2,7 +2,9 @@
 (networks/resnet.py:7-10, 56-58) against torch fp64 convolutions: forward with the fused input BatchNorm and the statistics epilogue (one partial per row of tiles or per
 image), the F(2x2) operand it leaves for the weight gradient (bitwise the one F(2x2)'s own transform writes), data gradient with the ReLU gate (recomputed and byte-mask)
 and its partial sums, ragged maps, and the per-product dispatch rule.  Error bounds: F(4x4)'s transforms multiply by constants up to 8 and 16/15, so it is 2-3x further
-from fp64 than the direct kernels (profiles/r04_probe_winograd44.txt) - the bound here is 4e-6 where F(2x2)'s is 2e-6."""
+from fp64 than the direct kernels (profiles/r04_probe_winograd44.txt) - the bound here is 4e-6 where F(2x2)'s is 2e-6.  This file runs the whole chain through
+ops.*; every transform and batched product ON ITS OWN against fp64 - narrow channel counts, ragged maps, guards, partials group by group, refusals - is
+tests/test_gpu_wino_forms.py."""
 import numpy as np
 import pytest
 import torch
