@@ -1722,7 +1722,8 @@ def can_row_stem(w_shape):
 def stem_weight_rows(w):
     """[K,3,R,S] filter (OHWI memory) -> [K*R][24]: its rows of 3 S floats, (s, c) order, zero-padded to 24."""
     w, (k, c, r, s_) = _ohwi(w)
-    return pad_channels(w.permute(0, 2, 3, 1).reshape(k * r, s_ * c), 24)
+    rows = w.permute(0, 2, 3, 1).reshape(k * r, s_ * c)
+    return rows if s_ * c == 24 else pad_channels(rows, 24)          # 8 taps fill the 24 floats: nothing to pad (ssv_pad_channels refuses cin == cout)
 
 
 def stem_conv_fwd(x, wrows, w_shape, stride, pad, want_stats=False):
