@@ -607,7 +607,7 @@ int ssv_cluster_votes(int64_t n, const int32_t* pred, const int32_t* targets, in
  *   fp32 is optional (NULL).  An idx outside [0, n) or a label outside [0, C) is not counted and sets *flag (device int32, zeroed by the call); an entry whose sim
  *   is NaN is not counted.  Limits: 1 <= m <= 2^30, 1 <= k <= SSV_KNN_MAX_K, 1 <= n < 2^31, 1 <= C <= SSV_KNN_MAX_CLASSES, 1 <= topn <= min(C, SSV_KNN_MAX_TOPN),
  *   inv_temp finite and positive; the outputs alias neither each other nor an input.
- * Not built: a search fused into the product, approximate search, exclusion of the query itself, k > 1024.
+ * Not built: a search fused into the product for k > 1 (k = 1: ssv_nn_lookup below), approximate search, exclusion of the query itself, k > 1024.
  * The ABI version stays 124: entry points were only added, and the binding refuses a library that lacks a declared symbol when it loads. */
 #define SSV_KNN_MAX_K 1024
 #define SSV_KNN_MAX_D 8192
@@ -618,6 +618,39 @@ int ssv_knn_search(int64_t m, int64_t n, int32_t d, int32_t k, const float* quer
                    int32_t arithmetic, int32_t chunk_rows, int32_t part_cols, void* ws, size_t ws_bytes, void* stream);
 int ssv_knn_vote(int64_t m, int32_t k, int64_t n, int32_t num_classes, int32_t topn, const float* sim, const int32_t* idx, const int32_t* bank_labels,
                  float inv_temp, int32_t* pred, float* scores, int32_t* flag, void* stream);
+
+/* ---- the nearest-neighbour lookup of NNCLR (csrc/nnlookup.hip; Dwibedi et al., ICCV 2021): every embedding of a step is replaced by its nearest neighbour in a
+ * support queue of past embeddings.  The top-1 search FUSED into the product, and the gather of the winning row.  The reference has no such trainer.
+ *
+ * ssv_nn_lookup: queries [m][d], bank [>= n][d] fp32, dense.  For every query i:
+ *   result  idx[i] = the j in [0, n) with the largest s_ij = q_i . b_j; sim[i] = that score, with the bits the product produced; nn[i][:] = out_scale * bank[idx[i]][:],
+ *          one fp32 multiply per element (nn may be NULL: idx and sim are the same).
+ *   order  the best starts at (-inf, index 0); only a STRICTLY greater score replaces it and candidates are folded in ascending j.  So exact ties go to the lowest j,
+ *          a NaN score never wins, and a query with no winning score (all its scores NaN or -inf) returns idx 0, sim -inf and row 0.
+ *   duplicates  bit-identical bank rows score bit-identically within a call wherever they sit - same tile, another tile, another workgroup or slice, the ragged
+ *          last tile (one instruction sequence per bank row whatever its position) - so a duplicate never beats its first copy.
+ *   bounds  rows of bank behind n are never read into a result (models/moco.py's MemoryBank pads its queue to a multiple of 16 rows).
+ *   determinism  no floating-point atomics; equal inputs give equal bits whatever the workspace held before.
+ *   arithmetic  SSV_ARITH_BF16X3 with d % 32 == 0 and d <= SSV_NN_LOOKUP_FUSED_MAX_D: fused.  S never reaches memory: the bank is streamed once per block of 256
+ *          queries in fp32 and split into bf16 pieces in registers, the queries are split once per call; the six-product accumulation of csrc/split_bf16.h on
+ *          v_mfma_f32_32x32x16_bf16 with a lane owning a query, so the arg-max over a tile's bank rows is a compare-select inside the lane.  A workgroup takes one
+ *          slice of the bank - L = SSV_NN_LOOKUP_SLICE * ceil(ceil(n / SSV_NN_LOOKUP_SLICE) / SSV_NN_LOOKUP_MAX_SLICES) rows: SSV_NN_LOOKUP_SLICE up to 2^21 rows -
+ *          and 256 queries, and leaves per-slice (score, index) partials in the workspace; a second kernel folds them in ascending slice order and writes idx, sim
+ *          and the scaled gathered row.  SSV_ARITH_F32_MFMA, or a width the fused kernel does not take (these run WHOLLY on fp32 MFMA): S by chunks of 1024 queries
+ *          and parts of the bank (the partition of ssv_knn_search) through ssv_conv2d_fwd into the workspace, one wavefront per row folding each part into the
+ *          running best, then the same second kernel.  Same contract.
+ *   limits  1 <= m <= SSV_NN_LOOKUP_MAX_M, 1 <= n < 2^31, d % 4 == 0, 4 <= d <= SSV_KNN_MAX_D, out_scale finite, all pointers 16-byte aligned, the outputs alias neither
+ *          each other nor an input nor the workspace, ws_bytes >= ssv_nn_lookup_workspace_bytes(m, n, d, arithmetic) (0 for a refused shape).  Anything else returns
+ *          SSV_ERR_INVALID (a short workspace too) with a message that starts "ssv_nn_lookup:"; nothing is clamped and no output is touched.
+ * Not built: k > 1, approximate or reduced-precision candidate search, queue planes kept across calls, the data-parallel form.
+ * The ABI version stays 124: entry points were only added. */
+#define SSV_NN_LOOKUP_MAX_M 8192
+#define SSV_NN_LOOKUP_FUSED_MAX_D 1024
+#define SSV_NN_LOOKUP_SLICE 512
+#define SSV_NN_LOOKUP_MAX_SLICES 4096
+size_t ssv_nn_lookup_workspace_bytes(int32_t m, int64_t n, int32_t d, int32_t arithmetic);
+int ssv_nn_lookup(int32_t m, int64_t n, int32_t d, const float* queries, const float* bank, float out_scale, float* nn, int32_t* idx, float* sim,
+                  int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
 
 /* ==== "next" row 1 of the scope table: DINO on the reference's ViT (networks/vit.py, models/dino.py) ====================
  * Linear layers of the encoder and of the projection head are ssv_conv2d_fwd/dgrad/wgrad with H = W = R = S = 1 over

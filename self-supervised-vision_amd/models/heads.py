@@ -4,6 +4,7 @@ Parameter names, shapes and init draws follow the reference so state_dicts and s
   BYOL   MLP             models/byol.py:24-34     fc1 bn1 fc2
   Barlow ProjectionHead  models/barlow.py:23-36   layer1.{0,1} layer2.{0,1} layer3, then L2-normalise
   VICReg ProjectionHead  (not in the reference)   Barlow's three layers without the final L2 normalisation
+  NNCLR  Projection/PredictionHead  (not in the reference)   layer1.{0,1} layer2.{0,1} layer3.{0,1}  /  layer1.{0,1} layer2
 """
 import math
 
@@ -65,6 +66,39 @@ class BarlowProjectionHead(hnn.HipModule):
     def _run(self, tape, x):
         x = self.layer2._run(tape, self.layer1._run(tape, x))
         return hnn.l2_normalize(tape, self.layer3._run(tape, x))
+
+
+class _LinearBn(nn.Sequential):
+    def __init__(self, din, dout):
+        super().__init__(_fresh_linear(din, dout), hnn.HipBatchNorm(dout))
+
+    def _run(self, tape, x):
+        return hnn.batchnorm(tape, self[0]._run(tape, x), self[1])
+
+
+class NnclrProjectionHead(hnn.HipModule):
+    """NNCLR's projector (Dwibedi et al. 2021, section 4.1): Linear-BN-ReLU, Linear-BN-ReLU, Linear-BN.  The loss normalises its output."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim):
+        super().__init__()
+        self.layer1 = _LinearBnRelu(input_dim, hidden_dim)
+        self.layer2 = _LinearBnRelu(hidden_dim, hidden_dim)
+        self.layer3 = _LinearBn(hidden_dim, output_dim)
+
+    def _run(self, tape, x):
+        return self.layer3._run(tape, self.layer2._run(tape, self.layer1._run(tape, x)))
+
+
+class NnclrPredictionHead(hnn.HipModule):
+    """NNCLR's predictor: Linear-BN-ReLU, Linear, back to the projector's width."""
+
+    def __init__(self, dim, hidden_dim):
+        super().__init__()
+        self.layer1 = _LinearBnRelu(dim, hidden_dim)
+        self.layer2 = _fresh_linear(hidden_dim, dim)
+
+    def _run(self, tape, x):
+        return self.layer2._run(tape, self.layer1._run(tape, x))
 
 
 class VicregProjectionHead(BarlowProjectionHead):

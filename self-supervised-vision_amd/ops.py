@@ -988,6 +988,62 @@ def knn_vote(sim, idx, bank_labels, num_classes, temperature, topn=1, return_sco
     return (pred, scores) if return_scores else pred
 
 
+# ------------------------------------------------------------------------------------------- NNCLR's pieces: the nearest-neighbour lookup (csrc/nnlookup.hip), the cross-entropy
+def nn_lookup_slice_rows(n):
+    """Bank rows one workgroup of the fused lookup folds before its partial result leaves for the workspace (include/ssv_hip.h: ssv_nn_lookup, `arithmetic`):
+    rows [s * L, (s + 1) * L) form slice s."""
+    n = int(n)
+    if not 1 <= n < 1 << 31:
+        raise _lib.SsvError(f"nn_lookup_slice_rows: need 1 <= n < 2^31 (got {n})")
+    slices = -(-n // _lib.NN_LOOKUP_SLICE)
+    return _lib.NN_LOOKUP_SLICE * -(-slices // _lib.NN_LOOKUP_MAX_SLICES)
+
+
+def softmax_ce(logits, labels, classes=None, want_grad=True):
+    """(stats [2], dlogits or None) of a dense logit matrix [N, ld] whose first ``classes`` columns are valid (default all) against int32 labels [N]: stats[0] = the
+    mean cross-entropy, stats[1] = the fraction of rows whose arg-max is the label, dlogits [N, ld] = d(mean loss) / dlogits with zeros in the pad columns
+    (ssv_softmax_ce_fwd_bwd, the linear probe's kernel)."""
+    _lib._dev(logits, labels)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous() or labels.dtype != torch.int32 or labels.shape != (logits.shape[0],) or not labels.is_contiguous():
+        raise _lib.SsvError("softmax_ce: a contiguous fp32 matrix logits [N, ld] and contiguous int32 labels [N] expected")
+    n, ld = logits.shape
+    c = ld if classes is None else int(classes)
+    if not 1 <= c <= ld:
+        raise _lib.SsvError(f"softmax_ce: need 1 <= classes <= {ld} columns (got {c})")
+    stats = _empty((2,), logits)
+    dlog = torch.empty_like(logits) if want_grad else None
+    ws = workspace.get(_lib.load().ssv_softmax_ce_workspace_bytes(n), logits.device)
+    call("ssv_softmax_ce_fwd_bwd", n, c, ld, ptr(logits), ptr(labels), ptr(stats), ptr(dlog), ptr(ws), ws.numel(), stream())
+    return stats, dlog
+
+
+def nn_lookup(queries, bank, n=None, out_scale=1.0, want_rows=True):
+    """(nn [m, d] fp32 or None, idx [m] int32, sim [m] fp32): for every row of queries [m, d] the row j < n of bank [>= n, d] with the largest inner product - exact
+    ties to the lowest j, a NaN score never wins - as idx, its score as sim, and out_scale * bank[idx] as nn (``want_rows``).  ``n``: the rows of the bank that
+    are searched (default all; a MemoryBank's pad rows stay outside).  Contiguous fp32 device matrices, d % 4 == 0, m <= 8192.  Only enqueues: no host
+    synchronisation, capturable in a step graph."""
+    _lib._dev(queries, bank)
+    if queries.dim() != 2 or bank.dim() != 2 or queries.dtype != torch.float32 or bank.dtype != torch.float32:
+        raise _lib.SsvError(f"nn_lookup: fp32 matrices queries [m, d] and bank [rows, d] expected (got {tuple(queries.shape)} {queries.dtype}, {tuple(bank.shape)} {bank.dtype})")
+    if not queries.is_contiguous() or not bank.is_contiguous():
+        raise _lib.SsvError("nn_lookup: queries and bank must be contiguous")
+    (m, d), (rows, db) = queries.shape, bank.shape
+    n = rows if n is None else int(n)
+    if db != d or d < 4 or d % 4 or d > _lib.KNN_MAX_D:
+        raise _lib.SsvError(f"nn_lookup: queries have {d} columns, the bank {db}; d % 4 == 0 and 4 <= d <= {_lib.KNN_MAX_D}")
+    if not 1 <= m <= _lib.NN_LOOKUP_MAX_M or not 1 <= n <= rows:
+        raise _lib.SsvError(f"nn_lookup: need 1 <= m <= {_lib.NN_LOOKUP_MAX_M} and 1 <= n <= the bank's {rows} rows (got m = {m}, n = {n})")
+    if not math.isfinite(float(out_scale)):
+        raise _lib.SsvError(f"nn_lookup: out_scale must be finite (got {out_scale})")
+    arith = _arith_code()
+    ws = workspace.get(max(_lib.load().ssv_nn_lookup_workspace_bytes(m, n, d, arith), 16), queries.device)
+    nn = torch.empty((m, d), dtype=torch.float32, device=queries.device) if want_rows else None
+    idx = torch.empty(m, dtype=torch.int32, device=queries.device)
+    sim = torch.empty(m, dtype=torch.float32, device=queries.device)
+    call("ssv_nn_lookup", m, n, d, ptr(queries), ptr(bank), float(out_scale), ptr(nn), ptr(idx), ptr(sim), arith, ptr(ws), ws.numel(), stream())
+    return nn, idx, sim
+
+
 # ------------------------------------------------------------------------------------------- ViT / DINO pieces
 LN_EPS = 1e-5
 ATTENTION_BF16X3 = True      # the attention forward's two products in the bf16x3 arithmetic when ops.ARITHMETIC says so (the backward stays on the fp32 instruction)

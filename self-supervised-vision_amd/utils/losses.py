@@ -239,6 +239,75 @@ class VicregLoss(nn.Module):
         return _VicregFn.apply(x, y, self)
 
 
+def nnclr_pair(a, p, labels):
+    """One direction of the NNCLR loss and its gradient: (stats, dp) with stats[0] = mean_i CE_i(A P_hat^T) - ``a`` [B, D] the neighbours already scaled by 1 / T,
+    P_hat = l2norm(p) - and dp = d stats[0] / dp.  Row-direction cross-entropy only (the paper's eq. 3)."""
+    b, d = p.shape
+    bp = (b + 3) // 4 * 4                    # the weight-gradient GEMM takes whole float4s of dlogits: the logit matrix is [B, bp], its pad columns products with zero rows
+    phat = torch.empty((bp, d), dtype=torch.float32, device=p.device)
+    if bp > b:
+        ops.fill_(phat[b:], 0.0)
+    _, inv = ops.l2norm_fwd(p, True, out=phat[:b])
+    a4 = a.view(b, 1, 1, d)
+    logits = ops.conv2d_fwd(a4, phat).view(b, bp)                                     # logits[i][j] = a_i . p_hat_j
+    stats, dlog = ops.softmax_ce(logits, labels, classes=b)                           # the pad columns of dlogits are zeros
+    dphat = torch.empty_like(phat)
+    ops.conv2d_wgrad(a4, dlog.view(b, 1, 1, bp), phat, dphat, accumulate=False)         # dP_hat = dlogits^T A
+    dp = ops.l2norm_bwd(phat[:b], inv, dphat[:b], d, True)
+    ops.drop_planes(phat)                    # P_hat is no weight: its bf16 planes must not wait in the cache for the next optimizer step
+    return stats, dp
+
+
+class _NnclrFn(torch.autograd.Function):
+    """Lookup (both views' embeddings, stacked: the bank is read once per step), the two cross-entropies and their gradients in forward; backward only scales."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, z1, z2, bank, queue_size, module):
+        b, d = p1.shape
+        zq = torch.empty((2 * b, d), dtype=torch.float32, device=p1.device)
+        ops.l2norm_fwd(z1.detach().contiguous(), True, out=zq[:b])
+        ops.l2norm_fwd(z2.detach().contiguous(), True, out=zq[b:])
+        nn_, module.last_idx, module.last_sim = ops.nn_lookup(zq, bank, n=queue_size, out_scale=1.0 / module.temperature)
+        labels = torch.arange(b, dtype=torch.int32, device=p1.device)
+        s12, dp2 = nnclr_pair(nn_[:b], p2.detach().contiguous(), labels)               # (nn1, p2)
+        s21, dp1 = nnclr_pair(nn_[b:], p1.detach().contiguous(), labels)               # (nn2, p1)
+        half = torch.full((1,), 0.5, dtype=torch.float32, device=p1.device)
+        loss = ops.scale_(ops.add_(s12[:1], s21[:1]), half)
+        ctx.saved = (ops.scale_(dp1, half), ops.scale_(dp2, half))
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dp1, dp2 = ctx.saved
+        g = dloss.contiguous()
+        return ops.scale_(dp1, g), ops.scale_(dp2, g), None, None, None, None, None
+
+
+class NnclrLoss(nn.Module):
+    """NNCLR (Dwibedi et al., ICCV 2021; not in the reference): 1/2 (CE(NN(z1) . p2^T / T) + CE(NN(z2) . p1^T / T)) with NN(z) the nearest neighbour of the
+    normalised, detached projection in the support queue ``bank`` [>= queue_size, D] (models.moco.MemoryBank) and p the L2-normalised predictions.  Gradients reach
+    p1 and p2 only.  D % 4 == 0 (a multiple of 32 takes the fused lookup).  ``last_idx`` (device int32 [2B]) / ``last_sim``: the neighbours of the last forward."""
+
+    def __init__(self, temperature=0.1):
+        super().__init__()
+        self.temperature = float(temperature)
+        if not self.temperature > 0.0:
+            raise ValueError(f"NnclrLoss: the temperature must be positive (got {temperature})")
+        self.last_idx = self.last_sim = None
+
+    def forward(self, z1, z2, p1, p2, bank, queue_size=None):
+        shapes = {tuple(t.shape) for t in (z1, z2, p1, p2)}
+        if p1.dim() != 2 or len(shapes) != 1:
+            raise ValueError(f"NnclrLoss expects four [B,D] matrices of one shape, got {[tuple(t.shape) for t in (z1, z2, p1, p2)]}")
+        n = bank.shape[0] if queue_size is None else int(queue_size)
+        if bank.dim() != 2 or bank.shape[1] != p1.shape[1] or not 1 <= n <= bank.shape[0] or p1.shape[1] % 4 or 2 * p1.shape[0] > _lib.NN_LOOKUP_MAX_M:
+            raise ValueError(f"NnclrLoss needs a bank [>= queue_size, D] with D % 4 == 0 and B <= {_lib.NN_LOOKUP_MAX_M // 2}, got bank {tuple(bank.shape)}, "
+                             f"queue_size {n}, embeddings {tuple(p1.shape)}")
+        if hdist.is_on():
+            raise NotImplementedError("NnclrLoss is single-process: the support queue is not replicated across ranks")
+        return _NnclrFn.apply(p1, p2, z1, z2, bank, n, self)
+
+
 # ------------------------------------------------------------------------------------------- sibling algorithms
 class _NegDotPairFn(torch.autograd.Function):
     """0.5 * (SimSiamLoss(o1, t2) + SimSiamLoss(o2, t1)) (utils/losses.py:145-152, models/simsiam.py:126-127); the mean runs over

@@ -24,6 +24,7 @@ CLASSES = (
     ("misc", "nhwc_to_nchw_k"), ("misc", "queue_push_k"), ("misc", "queue_advance_k"), ("misc", "vit_embed_"), ("misc", "split_planes_k"), ("misc", "bank_momentum_k"), ("misc", "patch_split_k"),
     ("misc", "kmeans_"), ("misc", "zero_i32_k"), ("misc", "cluster_votes_k"), ("misc", "votes_zero_k"),
     ("misc", "knn_select_k"), ("misc", "knn_merge_k"), ("misc", "knn_vote_k"), ("misc", "knn_flag_zero_k"),
+    ("misc", "nn_prep_k"), ("misc", "nn_fused_k"), ("misc", "nn_rowarg_k"), ("misc", "nn_fold_k"),
 )
 CONV_FAMILY = ("conv_fwd", "conv_dgrad", "conv_wgrad")
 # host functions whose kernels run under another class's scope than the table gives them - both inside the conv family, so the family sums agree:
