@@ -652,6 +652,50 @@ size_t ssv_nn_lookup_workspace_bytes(int32_t m, int64_t n, int32_t d, int32_t ar
 int ssv_nn_lookup(int32_t m, int64_t n, int32_t d, const float* queries, const float* bank, float out_scale, float* nn, int32_t* idx, float* sim,
                   int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the batched whitening of W-MSE (csrc/whiten.hip; Ermolov, Siarohin, Sangineto, Sebe, ICML 2021): the embeddings of a view are whitened inside small
+ * random sub-batches ("blocks") and the loss is the MSE between the normalised whitened positives.  The reference has no such trainer.  All matrices are dense
+ * row-major fp32.  For one block of w rows (indices rows[b][0 .. w) into x) of width d:
+ *     mu = column mean,  xc = x[rows] - mu,  S = xc^T xc / (w - 1),  A = (1 - eps) S + eps I = L L^T (L lower),  W = L^-1,  y = xc W^T   (cov(y) = I at eps = 0)
+ *
+ * ssv_whiten_fwd: x [n_rows][d], rows int32 [blocks][w]; y [blocks * w][d] block-dense (row b * w + i is the whitened x[rows[b][i]]), mean [blocks][d] and
+ *   winv [blocks][d][d] (W as a full lower-triangular matrix with exact zeros above the diagonal) are saved for the backward; info int32 [blocks].
+ *   centring  the rows are centred first (by the fp32 mean that is stored) and the covariance is formed from the centred rows; no one-pass E[x^2] - E[x]^2.
+ *   accumulation  every sum runs in double in a fixed order, there are no floating-point atomics: equal inputs give equal bits whatever the workspace held.
+ *   pivots  info[b] = 0 on success; info[b] = j + 1 when pivot j of block b, rounded to fp32, is not a positive finite number.  That pivot is never clamped: the
+ *          block's rows of y and its winv are filled with NaN (its mean is valid).  Every other block is unaffected, bit for bit.
+ *   bounds  a row index outside [0, n_rows) is never dereferenced: the block gets info[b] = -1 and NaN in y, mean and winv.
+ *   limits  1 <= blocks, blocks * w < 2^31, d % 4 == 0, 4 <= d <= SSV_WHITEN_MAX_D, d < w <= SSV_WHITEN_MAX_W, 1 <= n_rows < 2^31, 0 <= eps < 1, all pointers
+ *          16-byte aligned, the outputs alias neither each other nor an input nor the workspace, ws_bytes >= ssv_whiten_workspace_bytes(blocks, w, d) (0 for a
+ *          refused shape; the workspace holds the centred rows between the two passes of a block).  Anything else returns SSV_ERR_INVALID with a message that
+ *          starts "ssv_whiten_fwd:"; nothing is clamped and no output is touched.
+ * ssv_whiten_bwd: dy [blocks * w][d], dx [n_rows][d] indexed like x.  dx[rows[b][i]] is WRITTEN, not accumulated; rows of dx that no block names are left
+ *   untouched.  THE INDICES OF ONE CALL MUST BE DISTINCT (as for ssv_bank_momentum_update: two blocks naming one row would race).  With G the block's dy:
+ *       dW = G^T xc,  dL = tril(-W^T dW W^T),  P = Phi(L^T dL)  (Phi: lower triangle, diagonal halved),  dA = sym(W^T P W),
+ *       g = G W + 2 (1 - eps) / (w - 1) xc dA,  dx[rows] = g - column mean of g
+ *   evaluated without L: L^T dL = -dW W^T on the lower triangle, and the column mean of g is that of G W because xc has zero column sums.  Blocks whose saved
+ *   winv is NaN produce NaN rows; a block with an index out of range writes NaN to the rows it can name.  Same limits and refusals ("ssv_whiten_bwd:").
+ * ssv_wmse_perm: perm int32 [iters][views][n].  perm[t][0][:] is a permutation of 0 .. n - 1: position i draws the first word of the Philox4x32-10 block with
+ *   key seed and counter (i, (2048 + t) << 16, step, 0) (csrc/philox.h, the augmentation's generator; its view keys end below 2048), the positions are sorted by
+ *   their draw, ties to the lower position.  perm[t][v][i] = perm[t][0][i] + v * n.  step_dev non-NULL (int64 in device memory, 8-byte aligned): the kernel reads
+ *   the step from it and a second launch advances it by one behind it (the pattern of ssv_queue_push_counted), so no launch argument changes from step to step and a
+ *   replayed step draws a new permutation; NULL: the `step` argument is used.  Only the low 32 bits of the step enter the counter.
+ *   Limits: 2 <= n <= SSV_WMSE_PERM_MAX_N, 1 <= views <= SSV_WMSE_PERM_MAX_VIEWS, 1 <= iters <= SSV_WMSE_PERM_MAX_ITERS, perm 16-byte aligned.
+ * Layout: one workgroup of 1024 threads per block, the d x d matrices in LDS (up to the whole 160 KiB of a CU at d = 128), one launch per direction.
+ * Not built: the running whitening statistics for evaluation (this project evaluates on the encoder's features, like its other trainers), more than two views in
+ * the loss, d > 128, ZCA or iterative (Newton-Schulz) whitening, the data-parallel form.
+ * The ABI version stays 124: entry points were only added. */
+#define SSV_WHITEN_MAX_D 128
+#define SSV_WHITEN_MAX_W 1024
+#define SSV_WMSE_PERM_MAX_N 4096
+#define SSV_WMSE_PERM_MAX_VIEWS 8
+#define SSV_WMSE_PERM_MAX_ITERS 16
+size_t ssv_whiten_workspace_bytes(int32_t blocks, int32_t w, int32_t d);
+int ssv_whiten_fwd(int32_t blocks, int32_t w, int32_t d, int64_t n_rows, const float* x, const int32_t* rows, float eps, float* y, float* mean, float* winv,
+                   int32_t* info, void* ws, size_t ws_bytes, void* stream);
+int ssv_whiten_bwd(int32_t blocks, int32_t w, int32_t d, int64_t n_rows, const float* x, const int32_t* rows, float eps, const float* mean, const float* winv,
+                   const float* dy, float* dx, void* ws, size_t ws_bytes, void* stream);
+int ssv_wmse_perm(int32_t n, int32_t views, int32_t iters, uint64_t seed, uint64_t step, int64_t* step_dev, int32_t* perm, void* stream);
+
 /* ==== "next" row 1 of the scope table: DINO on the reference's ViT (networks/vit.py, models/dino.py) ====================
  * Linear layers of the encoder and of the projection head are ssv_conv2d_fwd/dgrad/wgrad with H = W = R = S = 1 over
  * N = B*T token rows; what follows are the pieces that are not GEMMs.  All matrices are dense row-major fp32. */

@@ -20,6 +20,7 @@
 //                       box-blur passes (BoxBlur.c: rows x 3, columns x 3, uint32 fixed point, uint8 between passes) ping-pong between two LDS
 //                       buffers, and the last one is normalised into the fp32 output.  No pass touches HBM.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -28,36 +29,6 @@ constexpr int KMAX = 8;                   // taps per axis: covers down-scaling 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 
 struct AugCfg { double brightness, contrast, saturation, hue, p_jitter, p_gray, p_flip, scale_min, scale_max, ratio_min, ratio_max; };
-
-// ---- Philox4x32-10 ------------------------------------------------------------------------------
-struct Philox {
-  uint32_t c[4], k[2], buf[4];
-  int left;
-  __device__ Philox(uint64_t seed, uint64_t step, uint64_t sample, uint32_t view) {
-    k[0] = (uint32_t)seed; k[1] = (uint32_t)(seed >> 32);
-    c[0] = (uint32_t)sample; c[1] = ((uint32_t)(sample >> 32) & 0xFFFFu) | ((view & 0xFFFFu) << 16);
-    c[2] = (uint32_t)step; c[3] = 0; left = 0;
-  }
-  __device__ void block() {
-    uint32_t x0 = c[0], x1 = c[1], x2 = c[2], x3 = c[3], k0 = k[0], k1 = k[1];
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      const uint32_t lo0 = 0xD2511F53u * x0, hi0 = __umulhi(0xD2511F53u, x0);
-      const uint32_t lo1 = 0xCD9E8D57u * x2, hi1 = __umulhi(0xCD9E8D57u, x2);
-      const uint32_t n0 = hi1 ^ x1 ^ k0, n1 = lo1, n2 = hi0 ^ x3 ^ k1, n3 = lo0;
-      x0 = n0; x1 = n1; x2 = n2; x3 = n3;
-      k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    buf[0] = x0; buf[1] = x1; buf[2] = x2; buf[3] = x3;
-    c[3] += 1; left = 4;
-  }
-  __device__ double uniform() {
-    if (left == 0) block();
-    const uint32_t v = buf[4 - left];
-    --left;
-    return (double)v * (1.0 / 4294967296.0);
-  }
-};
 
 // RandomResizedCrop.get_params: 10 attempts of (area ~ U[scale], log-ratio ~ U[log ratio]), then the centre-crop fallback
 __device__ void sample_rrc(Philox& st, int Hs, int Ws, double scale_min, double scale_max, double ratio_min, double ratio_max,

@@ -5,6 +5,7 @@ Parameter names, shapes and init draws follow the reference so state_dicts and s
   Barlow ProjectionHead  models/barlow.py:23-36   layer1.{0,1} layer2.{0,1} layer3, then L2-normalise
   VICReg ProjectionHead  (not in the reference)   Barlow's three layers without the final L2 normalisation
   NNCLR  Projection/PredictionHead  (not in the reference)   layer1.{0,1} layer2.{0,1} layer3.{0,1}  /  layer1.{0,1} layer2
+  W-MSE  ProjectionHead  (not in the reference)   layer1.{0,1} layer2, not normalised
 """
 import math
 
@@ -12,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import nn as hnn
+from .. import ops
 
 
 def _fresh_linear(din, dout):
@@ -99,6 +101,48 @@ class NnclrPredictionHead(hnn.HipModule):
 
     def _run(self, tape, x):
         return self.layer2._run(tape, self.layer1._run(tape, x))
+
+
+def _narrow_linear(tape, x, lin):
+    """hnn.linear for a layer whose output is narrower than the data-gradient kernels take (they contract over Dout in steps of 16): forward and weight gradient are
+    the usual launches, the data gradient runs on dy and the weight padded with zero columns / rows to the next multiple of 16."""
+    weight, bias = lin.weight, lin.bias
+    b, din = x.shape
+    dout = weight.shape[0]
+    x4 = x.view(b, 1, 1, din)
+    y = ops.conv2d_fwd(x4, weight, 1, 0, bias=bias).view(b, dout)
+    if tape is not None:
+        need_dx, slot = tape.needs_grad(x), tape.slot
+
+        def bwd(dy, existing):
+            ops.conv2d_wgrad(x4, dy.view(b, 1, 1, dout), weight, hnn.grad_of(weight, slot), 1, 0, accumulate=True, dbias=hnn.grad_of(bias, slot))
+            if not need_dx:
+                return (None,)
+            kp = (dout + 15) // 16 * 16
+            wp = torch.zeros((kp, din), dtype=torch.float32, device=x.device)
+            wp[:dout].copy_(weight.detach())
+            ex = existing[0]
+            ex4 = None if ex is None else ex.view(b, 1, 1, din)
+            dx = ops.conv2d_dgrad(ops.pad_channels(dy.contiguous(), kp).view(b, 1, 1, kp), wp, x4.shape, 1, 0, addend=ex4, out=ex4)
+            ops.drop_planes(wp)                  # the padded copy is no weight: its bf16 planes must not wait in the cache for the next optimizer step
+            return (dx.view(b, din),)
+        tape.record((x,), y, bwd)
+    return y
+
+
+class WmseProjectionHead(hnn.HipModule):
+    """W-MSE's projector (Ermolov et al. 2021, section 5): Linear-BN-ReLU, Linear.  The whitening fixes the scale of the output, so nothing is normalised.  The
+    embedding may be as narrow as 4 columns (the whitening's smallest width): see _narrow_linear."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim):
+        super().__init__()
+        self.layer1 = _LinearBnRelu(input_dim, hidden_dim)
+        self.layer2 = _fresh_linear(hidden_dim, output_dim)
+        self.narrow = output_dim % 16 != 0
+
+    def _run(self, tape, x):
+        h = self.layer1._run(tape, x)
+        return _narrow_linear(tape, h, self.layer2) if self.narrow else self.layer2._run(tape, h)
 
 
 class VicregProjectionHead(BarlowProjectionHead):

@@ -1044,6 +1044,59 @@ def nn_lookup(queries, bank, n=None, out_scale=1.0, want_rows=True):
     return nn, idx, sim
 
 
+# ------------------------------------------------------------------------------------------- W-MSE's pieces: the batched whitening and the permutation (csrc/whiten.hip)
+def _whiten_check(who, x, rows):
+    _lib._dev(x, rows)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or rows.dim() != 2 or rows.dtype != torch.int32 or not rows.is_contiguous():
+        raise _lib.SsvError(f"{who}: a contiguous fp32 matrix x [n_rows, d] and contiguous int32 rows [blocks, w] expected (got {tuple(x.shape)} {x.dtype}, {tuple(rows.shape)} {rows.dtype})")
+    (n_rows, d), (blocks, w) = x.shape, rows.shape
+    if d < 4 or d % 4 or d > _lib.WHITEN_MAX_D or not d < w <= _lib.WHITEN_MAX_W or blocks < 1:
+        raise _lib.SsvError(f"{who}: need d % 4 == 0, 4 <= d <= {_lib.WHITEN_MAX_D}, d < w <= {_lib.WHITEN_MAX_W} and at least one block (got d = {d}, w = {w}, blocks = {blocks})")
+    return n_rows, d, blocks, w
+
+
+def whiten_fwd(x, rows, eps=0.0):
+    """(y [blocks * w, d], mean [blocks, d], winv [blocks, d, d], info int32 [blocks]): every block rows[b] of w row indices into x [n_rows, d] is centred and whitened by
+    the inverse Cholesky factor of (1 - eps) cov + eps I (include/ssv_hip.h: ssv_whiten_fwd).  info[b] = 0, j + 1 for a failed pivot j, -1 for an index out of range
+    (the block's outputs are NaN then).  Only enqueues: no host synchronisation, capturable in a step graph."""
+    n_rows, d, blocks, w = _whiten_check("whiten_fwd", x, rows)
+    if not 0.0 <= float(eps) < 1.0:
+        raise _lib.SsvError(f"whiten_fwd: need 0 <= eps < 1 (got {eps})")
+    y = _empty((blocks * w, d), x)
+    mean = _empty((blocks, d), x)
+    winv = _empty((blocks, d, d), x)
+    info = torch.empty(blocks, dtype=torch.int32, device=x.device)
+    ws = workspace.get(_lib.load().ssv_whiten_workspace_bytes(blocks, w, d), x.device)
+    call("ssv_whiten_fwd", blocks, w, d, n_rows, ptr(x), ptr(rows), float(eps), ptr(y), ptr(mean), ptr(winv), ptr(info), ptr(ws), ws.numel(), stream())
+    return y, mean, winv, info
+
+
+def whiten_bwd(x, rows, eps, mean, winv, dy, dx=None):
+    """dx [n_rows, d]: the gradient of whiten_fwd's y with respect to x given dy [blocks * w, d]; the rows the blocks name are written, the others keep what ``dx``
+    held (zeros when it is allocated here).  The indices of one call must be distinct."""
+    n_rows, d, blocks, w = _whiten_check("whiten_bwd", x, rows)
+    _lib._dev(mean, winv, dy)
+    if tuple(mean.shape) != (blocks, d) or tuple(winv.shape) != (blocks, d, d) or tuple(dy.shape) != (blocks * w, d) or not (mean.is_contiguous() and winv.is_contiguous() and dy.is_contiguous()):
+        raise _lib.SsvError(f"whiten_bwd: contiguous mean [{blocks}, {d}], winv [{blocks}, {d}, {d}] and dy [{blocks * w}, {d}] expected")
+    if dx is None:
+        dx = torch.zeros_like(x) if blocks * w < n_rows else torch.empty_like(x)
+    ws = workspace.get(_lib.load().ssv_whiten_workspace_bytes(blocks, w, d), x.device)
+    call("ssv_whiten_bwd", blocks, w, d, n_rows, ptr(x), ptr(rows), float(eps), ptr(mean), ptr(winv), ptr(dy), ptr(dx), ptr(ws), ws.numel(), stream())
+    return dx
+
+
+def wmse_perm(n, views, iters, seed, step=0, step_dev=None, device=None):
+    """int32 [iters, views, n]: per iteration a permutation of 0 .. n - 1 (positions sorted by their Philox draw keyed by (seed, step, iteration)), view v offset
+    by v * n.  ``step_dev`` (an int64 device tensor of one element) replaces ``step`` and is advanced by one behind the launch."""
+    device = step_dev.device if step_dev is not None else device
+    if step_dev is not None and (step_dev.dtype != torch.int64 or step_dev.numel() != 1):
+        raise _lib.SsvError("wmse_perm: step_dev must be an int64 tensor of one element")
+    perm = torch.empty((int(iters), int(views), int(n)), dtype=torch.int32, device=device)
+    _lib._dev(perm)
+    call("ssv_wmse_perm", int(n), int(views), int(iters), int(seed), int(step), ptr(step_dev), ptr(perm), stream())
+    return perm
+
+
 # ------------------------------------------------------------------------------------------- ViT / DINO pieces
 LN_EPS = 1e-5
 ATTENTION_BF16X3 = True      # the attention forward's two products in the bf16x3 arithmetic when ops.ARITHMETIC says so (the backward stays on the fp32 instruction)

@@ -308,6 +308,92 @@ class NnclrLoss(nn.Module):
         return _NnclrFn.apply(p1, p2, z1, z2, bank, n, self)
 
 
+class _WmseTermFn(torch.autograd.Function):
+    """One iteration of W-MSE: the blocks of both views whitened in ONE call, the pairs normalised and compared, and the whole backward down to dh in forward;
+    backward only scales.  Rows of h that no block names (a ragged batch) get zero gradient."""
+
+    @staticmethod
+    def forward(ctx, h, rows, eps, module):
+        hc = h.detach().contiguous()
+        y, mean, winv, info = ops.whiten_fwd(hc, rows, eps)
+        module.last_info.append(info)
+        m, d = y.shape[0] // 2, y.shape[1]
+        y1, y2 = y[:m], y[m:]
+        n1, inv1 = ops.l2norm_fwd(y1, True)
+        n2, inv2 = ops.l2norm_fwd(y2, True)
+        # |n1 - n2|^2 = 2 - 2 cos per pair: ops.mse_pair returns scale * 2 sum_p |n1_p - n2_p|^2 and, as do1 / do2, the gradients of scale * sum_p |n1_p - n2_p|^2
+        # through ONE of the two (symmetric) terms each - so with scale = 1 / m the gradients are those of the mean and the loss is twice it
+        loss2, dn1, dn2 = ops.mse_pair(n1, n2, n1, n2, 1.0 / m)
+        half = torch.full((1,), 0.5, dtype=torch.float32, device=h.device)
+        loss = ops.scale_(loss2.view(1), half)
+        dy = torch.cat([ops.l2norm_bwd(n1, inv1, dn1, d, True), ops.l2norm_bwd(n2, inv2, dn2, d, True)])
+        ctx.saved = ops.whiten_bwd(hc, rows, eps, mean, winv, dy)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        return ops.scale_(ctx.saved, dloss.contiguous()), None, None, None
+
+
+class WmseLoss(nn.Module):
+    """W-MSE (Ermolov et al., ICML 2021; not in the reference), called as fn(z1, z2) with the [N, d] projections of the two views.  h = cat(z1, z2); per iteration t
+    (``w_iter`` of them) a device permutation of the batch (ops.wmse_perm, keyed by (seed, step, t); the step counter is a device tensor owned by this module and
+    advanced by every call, so a replayed step draws a new permutation) cuts each view into nb = N // w_size blocks of ``w_size`` rows - the same rows in both views, so
+    position p of the view-1 half is the positive of position p of the view-2 half - each block is whitened alone (ops.whiten_fwd, ``eps`` shrinks the covariance towards
+    I) and the term is 2 - 2 mean_p cos(y1_p, y2_p).  The loss is the mean of the terms.  A ragged batch trains on nb * w_size of its rows per iteration.
+    ``check=True`` (the eager default) reads the whitening's status back - one host synchronisation - and raises SsvError naming the block whose covariance has no
+    Cholesky factor; a step graph passes False.  ``last_perm``: the permutation tensor of the last call; ``last_info``: the status tensors of its iterations."""
+
+    def __init__(self, w_size, w_iter=1, eps=0.0, seed=0):
+        super().__init__()
+        self.w_size, self.w_iter, self.eps, self.seed = int(w_size), int(w_iter), float(eps), int(seed)
+        if not 1 <= self.w_iter <= _lib.WMSE_PERM_MAX_ITERS:
+            raise ValueError(f"WmseLoss: w_iter must be in [1, {_lib.WMSE_PERM_MAX_ITERS}] (got {w_iter})")
+        if not 0.0 <= self.eps < 1.0:
+            raise ValueError(f"WmseLoss: eps must be in [0, 1) (got {eps})")
+        if not 2 <= self.w_size <= _lib.WHITEN_MAX_W:
+            raise ValueError(f"WmseLoss: w_size must be in [2, {_lib.WHITEN_MAX_W}] (got {w_size})")
+        self.step_dev = None
+        self.last_perm, self.last_info = None, []
+
+    def reset_step(self, device, step=0):
+        """(re)create the device step counter: a trainer calls this once, before any step is captured into a graph"""
+        self.step_dev = torch.full((1,), int(step), dtype=torch.int64, device=device)
+        return self
+
+    def forward(self, z1, z2, check=True):
+        if z1.dim() != 2 or z1.shape != z2.shape:
+            raise ValueError(f"WmseLoss expects two [N,d] matrices of one shape, got {tuple(z1.shape)} and {tuple(z2.shape)}")
+        n, d = z1.shape
+        if d < 4 or d % 4 or d > _lib.WHITEN_MAX_D:
+            raise ValueError(f"WmseLoss: the embedding width must be a multiple of 4 in [4, {_lib.WHITEN_MAX_D}] (got {d})")
+        if self.w_size <= d:
+            raise ValueError(f"WmseLoss: w_size ({self.w_size}) must exceed the embedding width ({d}): the covariance of a block would be singular")
+        if n < self.w_size or n > _lib.WMSE_PERM_MAX_N:
+            raise ValueError(f"WmseLoss: the batch ({n}) must hold at least one block of w_size = {self.w_size} rows and at most {_lib.WMSE_PERM_MAX_N} rows")
+        if hdist.is_on():
+            raise NotImplementedError("WmseLoss is single-process: the sub-batches are drawn from one rank's batch")
+        if self.step_dev is None or self.step_dev.device != z1.device:
+            self.reset_step(z1.device)
+        nb = n // self.w_size
+        self.last_perm = perm = ops.wmse_perm(n, 2, self.w_iter, self.seed, step_dev=self.step_dev)
+        self.last_info = []
+        h = torch.cat([z1, z2])
+        total = None
+        for t in range(self.w_iter):
+            rows = perm[t, :, :nb * self.w_size].reshape(2 * nb, self.w_size).contiguous()
+            term = _WmseTermFn.apply(h, rows, self.eps, self)
+            total = term if total is None else total + term
+        if check:
+            for t, info in enumerate(self.last_info):
+                bad = info.cpu()
+                if int((bad != 0).sum()):
+                    b = int((bad != 0).nonzero()[0])
+                    raise _lib.SsvError(f"WmseLoss: iteration {t}, block {b} (view {b // nb + 1}, sub-batch {b % nb}): whitening status {int(bad[b])} "
+                                        "(j + 1: pivot j of the covariance's Cholesky factor is not positive; -1: an index out of range)")
+        return total if self.w_iter == 1 else total / self.w_iter
+
+
 # ------------------------------------------------------------------------------------------- sibling algorithms
 class _NegDotPairFn(torch.autograd.Function):
     """0.5 * (SimSiamLoss(o1, t2) + SimSiamLoss(o2, t1)) (utils/losses.py:145-152, models/simsiam.py:126-127); the mean runs over

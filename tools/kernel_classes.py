@@ -25,6 +25,7 @@ CLASSES = (
     ("misc", "kmeans_"), ("misc", "zero_i32_k"), ("misc", "cluster_votes_k"), ("misc", "votes_zero_k"),
     ("misc", "knn_select_k"), ("misc", "knn_merge_k"), ("misc", "knn_vote_k"), ("misc", "knn_flag_zero_k"),
     ("misc", "nn_prep_k"), ("misc", "nn_fused_k"), ("misc", "nn_rowarg_k"), ("misc", "nn_fold_k"),
+    ("loss", "whiten_fwd_k"), ("loss", "whiten_bwd_k"), ("misc", "wmse_perm_k"), ("misc", "wmse_step_advance_k"),
 )
 CONV_FAMILY = ("conv_fwd", "conv_dgrad", "conv_wgrad")
 # host functions whose kernels run under another class's scope than the table gives them - both inside the conv family, so the family sums agree:
