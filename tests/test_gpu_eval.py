@@ -79,7 +79,7 @@ def test_fused_knn_agrees_with_the_unfused_search_on_unit_features(dev):
 
 def test_knn_large_set_multi_chunk_property(dev):
     """n above one S chunk (4096 rows): planted duplicates - every vector appears exactly twice with the same label and is far
-    from everything else, so with k=1 (after dropping the best hit) the agreement count is exactly n."""
+    from everything else, so with k=1 (after dropping the best hit) the agreement count is exactly n.  Under both arithmetics and at d = 64 and d = 96: see below."""
     from ssv_amd import ops
     n_half, d = 6000, 64
     g = torch.Generator().manual_seed(9)
@@ -87,6 +87,15 @@ def test_knn_large_set_multi_chunk_property(dev):
     z = torch.cat([base, base])
     labels = torch.arange(n_half, dtype=torch.int32).repeat(2)
     assert ops.knn_label_agreement(z.to(dev), labels.to(dev), 1) == 2 * n_half
+    # d = 64 under the default arithmetic is the FUSED search, which has no row chunks: "f32" (three chunks of S: 4096, 4096, 3808 rows) and d = 96 (no fused
+    # kernel: the bf16x3 Gram product with pre-split planes, chunk by chunk) cross the boundary in both arithmetics
+    with ops.arithmetic("f32"):
+        assert ops.knn_label_agreement(z.to(dev), labels.to(dev), 1) == 2 * n_half
+    base = torch.nn.functional.normalize(torch.randn(n_half, 96, generator=g), dim=1)
+    z = torch.cat([base, base])
+    for arith in ("bf16x3", "f32"):
+        with ops.arithmetic(arith):
+            assert ops.knn_label_agreement(z.to(dev), labels.to(dev), 1) == 2 * n_half, arith
 
 
 def test_knn_rejects_bad_arguments(dev):
