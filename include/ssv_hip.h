@@ -696,6 +696,45 @@ int ssv_whiten_bwd(int32_t blocks, int32_t w, int32_t d, int64_t n_rows, const f
                    const float* dy, float* dx, void* ws, size_t ws_bytes, void* stream);
 int ssv_wmse_perm(int32_t n, int32_t views, int32_t iters, uint64_t seed, uint64_t step, int64_t* step_dev, int32_t* perm, void* stream);
 
+/* ---- ProtoNCE, the prototype term of Prototypical Contrastive Learning (csrc/protonce.hip; Li, Zhou, Xiong, Hoi, ICLR 2021).  The reference has no such trainer.
+ * q [m][d], protos [ktot][d], inv_phi [ktot] (1 / concentration of every prototype), labels int32 [segs][m]: dense row-major device memory.  seg_end [segs] is a
+ * HOST array of int64: segment s - one clustering - is the prototype rows [seg_end[s - 1], seg_end[s]) (seg_end[-1] = 0), ktot = seg_end[segs - 1], and labels[s][i]
+ * is an index INSIDE segment s.  With s_ij = (q_i . c_j) * inv_phi_j - the product in the call's arithmetic, then one fp32 multiply - and y = labels[s][i]:
+ *     lse[s][i] = log sum_{j in segment s} exp(s_ij)                                            [segs][m]
+ *     loss      = 1 / segs * sum_s mean_i (lse[s][i] - s_iy)                                     [1]
+ *     dq        = d loss / d q = 1 / (segs m) * sum_s (sum_j p_ij inv_phi_j c_j - inv_phi_y c_y)  [m][d],   p_ij = exp(s_ij - lse[s][i])
+ * The prototypes and inv_phi carry no gradient.
+ *   arithmetic  SSV_ARITH_BF16X3 with d % 32 == 0 and d <= SSV_PROTO_NCE_FUSED_MAX_D: fused.  Neither the scores nor the probabilities reach memory: one pass
+ *          of the shape of a flash-attention forward with nn_fused_k's operand plan (prototypes streamed in fp32 and split in registers as the A operand, queries
+ *          split once per call as the B operand, a lane owns a query), the second product P (inv_phi o C) accumulated in registers under the online rescale, the
+ *          tile of scaled prototypes read back transposed from LDS in the order in which P lies in the accumulators.  A workgroup takes one slice of one segment -
+ *          L = SSV_PROTO_NCE_SLICE * ceil(ceil(K_s / SSV_PROTO_NCE_SLICE) / SSV_PROTO_NCE_MAX_SLICES) rows, never across a segment boundary - and one or two tiles
+ *          of 32 queries; its four waves leave (max, sum, acc[d]) of their quarters in the workspace; a second kernel merges them in ascending order, then the
+ *          segments in ascending order, subtracts the positive rows and writes lse and dq; a third sums the rows' losses in a fixed order.
+ *          SSV_PROTO_NCE_FUSED_MAX_D is bounded by REGISTERS and LDS: a lane keeps d / 32 output tiles of 16 accumulators per query tile beside the score tile
+ *          and both products' operand pieces, and a workgroup keeps four 32 x d fp32 tiles in LDS - at d = 128 exactly the 64 KiB a kernel may declare.
+ *          SSV_ARITH_F32_MFMA, or another width (these run WHOLLY on fp32 MFMA): per segment and chunk of queries, S through ssv_conv2d_fwd into the workspace
+ *          (against a copy of the segment padded with zero rows to a multiple of 16), a row kernel that scales, reduces and overwrites S with d loss / d S, and
+ *          ssv_conv2d_dgrad accumulating dq.  Same contract.
+ *   determinism  no floating-point atomics; equal inputs give equal bits whatever the workspace held before.
+ *   bounds  rows of protos / inv_phi behind ktot and rows of q / labels behind m are never read; nothing is written outside loss, lse, dq, flag and the workspace.
+ *   bad device data  the call zeroes *flag, then sets bit 0 for a label outside [0, K_s) and bit 1 for an inv_phi that is not finite and positive.  The numeric
+ *          result is then unspecified; every access still stays in bounds (the label is clamped where it is an address).  The host reads the flag when it chooses to.
+ *   limits  1 <= m <= SSV_PROTO_NCE_MAX_M, 1 <= segs <= SSV_PROTO_NCE_MAX_SEGS, seg_end strictly increasing from at least 1, ktot < 2^31, d % 4 == 0,
+ *          4 <= d <= SSV_KNN_MAX_D, all pointers 16-byte aligned, the outputs alias neither each other nor an input nor the workspace, ws_bytes >=
+ *          ssv_proto_nce_workspace_bytes(m, ktot, d, segs, arithmetic) (0 for a refused shape; it covers every segmentation of ktot rows into segs segments).
+ *          Anything else returns SSV_ERR_INVALID with a message that starts "ssv_proto_nce:"; nothing is clamped and no output is touched.
+ * Not built: sampled negative prototypes (the paper's r), the instance-wise InfoNCE term on this kernel (MoCo's loss keeps its own), the data-parallel form.
+ * The ABI version stays 124: entry points were only added. */
+#define SSV_PROTO_NCE_MAX_M 8192
+#define SSV_PROTO_NCE_MAX_SEGS 8
+#define SSV_PROTO_NCE_FUSED_MAX_D 128
+#define SSV_PROTO_NCE_SLICE 256
+#define SSV_PROTO_NCE_MAX_SLICES 32
+size_t ssv_proto_nce_workspace_bytes(int32_t m, int64_t ktot, int32_t d, int32_t segs, int32_t arithmetic);
+int ssv_proto_nce(int32_t m, int32_t d, int32_t segs, const int64_t* seg_end, const float* q, const float* protos, const float* inv_phi, const int32_t* labels,
+                  float* loss, float* lse, float* dq, int32_t* flag, int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
+
 /* ==== "next" row 1 of the scope table: DINO on the reference's ViT (networks/vit.py, models/dino.py) ====================
  * Linear layers of the encoder and of the projection head are ssv_conv2d_fwd/dgrad/wgrad with H = W = R = S = 1 over
  * N = B*T token rows; what follows are the pieces that are not GEMMs.  All matrices are dense row-major fp32. */

@@ -88,6 +88,11 @@ def _close_all():
 atexit.register(_close_all)
 
 
+def _max_pixels(ins):
+    """Pixels per image of the largest image input; inputs that are no images (PCL's sample ``index``, a vector) do not count"""
+    return max((t.shape[-1] * t.shape[-2] for t in ins.values() if t.dim() >= 3), default=0)
+
+
 class StepGraph:
     """``sg = StepGraph(trainer); metrics = sg(batch)`` - the drop-in for ``trainer.train_step(batch)``.  ``weak=True`` (what TwoViewTrainer.step passes: the trainer
     holds its StepGraph) holds the trainer weakly: no reference cycle, so dropping the trainer destroys its graphs at once - by reference count, at a defined point -
@@ -146,7 +151,7 @@ class StepGraph:
             return "the optimizer is neither the fused SGD nor the fused AdamW nor the fused LARS"
         if not ins or not all(t.is_cuda for t in ins.values()):
             return "the batch is not on the GPU"
-        if self.mode == "auto" and max(t.shape[-1] * t.shape[-2] for t in ins.values()) > AUTO_MAX_PIXELS:
+        if self.mode == "auto" and _max_pixels(ins) > AUTO_MAX_PIXELS:
             return "images larger than 64 x 64: the step is GPU-bound (SSV_STEP_GRAPH=1 forces the graph)"
         return None
 
@@ -227,7 +232,7 @@ class StepGraph:
         graph = torch.cuda.CUDAGraph()
         eager_ws, ops.workspace.buf = ops.workspace.buf, {}
         prev = hnn.begin_capture(host)
-        small = max(t.shape[-1] * t.shape[-2] for t in ins.values()) <= AUTO_MAX_PIXELS
+        small = _max_pixels(ins) <= AUTO_MAX_PIXELS
         floors = ops.graph_dispatch() if (self.graph_floors and small) else None
         trainer = self.trainer
         gc_was_on = gc.isenabled()

@@ -1097,6 +1097,54 @@ def wmse_perm(n, views, iters, seed, step=0, step_dev=None, device=None):
     return perm
 
 
+# ------------------------------------------------------------------------------------------- PCL's piece: the fused ProtoNCE loss (csrc/protonce.hip)
+def proto_nce_route(d):
+    """"fused" or "unfused": the route ssv_proto_nce takes at width d under the current arithmetic (include/ssv_hip.h: ssv_proto_nce, `arithmetic`); the benchmark
+    (tools/bench_pcl.py) found no shape at which the fused route loses, so nothing else enters the choice"""
+    return "fused" if ARITHMETIC == "bf16x3" and d % 32 == 0 and d <= _lib.PROTO_NCE_FUSED_MAX_D else "unfused"
+
+
+def proto_nce(q, protos, inv_phi, labels, seg_end):
+    """(loss 0-d, lse [segs, m], dq [m, d], flag int32 [1]) of the ProtoNCE term: q [m, d] against the prototypes protos [ktot, d], cut by the python ints
+    ``seg_end`` into segments (one clustering each), with scores (q . c_j) * inv_phi[j] and labels [segs, m] int32 naming every query's prototype INSIDE each
+    segment: loss = 1 / segs * sum_s mean_i (lse[s, i] - s_iy), dq = d loss / dq (include/ssv_hip.h: ssv_proto_nce).  flag: bit 0 a label outside its segment,
+    bit 1 an inv_phi that is not finite and positive - left on the device for the caller to read when it chooses.  Contiguous device tensors, d % 4 == 0,
+    m <= 8192, at most 8 segments.  Only enqueues: no host synchronisation, capturable in a step graph."""
+    _lib._dev(q, protos, inv_phi, labels)
+    if q.dim() != 2 or protos.dim() != 2 or q.dtype != torch.float32 or protos.dtype != torch.float32 or inv_phi.dtype != torch.float32 or labels.dtype != torch.int32:
+        raise _lib.SsvError(f"proto_nce: fp32 q [m, d], protos [ktot, d], inv_phi [ktot] and int32 labels [segs, m] expected (got {tuple(q.shape)} {q.dtype}, "
+                            f"{tuple(protos.shape)} {protos.dtype}, {tuple(inv_phi.shape)} {inv_phi.dtype}, {tuple(labels.shape)} {labels.dtype})")
+    if not (q.is_contiguous() and protos.is_contiguous() and inv_phi.is_contiguous() and labels.is_contiguous()):
+        raise _lib.SsvError("proto_nce: q, protos, inv_phi and labels must be contiguous")
+    ends = [int(e) for e in seg_end]
+    (m, d), (rows, dc), segs = q.shape, protos.shape, len(ends)
+    if not 1 <= segs <= _lib.PROTO_NCE_MAX_SEGS or any(b <= a for a, b in zip([0] + ends, ends)) or ends[-1] > rows:
+        raise _lib.SsvError(f"proto_nce: seg_end must hold 1 to {_lib.PROTO_NCE_MAX_SEGS} strictly increasing positive row counts within the {rows} prototypes (got {ends})")
+    ktot = ends[-1]
+    if dc != d or d < 4 or d % 4 or d > _lib.KNN_MAX_D or not 1 <= m <= _lib.PROTO_NCE_MAX_M:
+        raise _lib.SsvError(f"proto_nce: q has {d} columns, the prototypes {dc}; d % 4 == 0, 4 <= d <= {_lib.KNN_MAX_D} and 1 <= m <= {_lib.PROTO_NCE_MAX_M} (got m = {m})")
+    if inv_phi.dim() != 1 or inv_phi.numel() < ktot or tuple(labels.shape) != (segs, m):
+        raise _lib.SsvError(f"proto_nce: inv_phi [>= {ktot}] and labels [{segs}, {m}] expected (got {tuple(inv_phi.shape)}, {tuple(labels.shape)})")
+    arith = _arith_code()
+    ws = workspace.get(max(_lib.load().ssv_proto_nce_workspace_bytes(m, ktot, d, segs, arith), 16), q.device)
+    loss = torch.empty((1,), dtype=torch.float32, device=q.device)
+    lse = torch.empty((segs, m), dtype=torch.float32, device=q.device)
+    dq = torch.empty((m, d), dtype=torch.float32, device=q.device)
+    flag = torch.empty(1, dtype=torch.int32, device=q.device)
+    call("ssv_proto_nce", m, d, segs, (C.c_int64 * segs)(*ends), ptr(q), ptr(protos), ptr(inv_phi), ptr(labels), ptr(loss), ptr(lse), ptr(dq), ptr(flag), arith,
+         ptr(ws), ws.numel(), stream())
+    return loss.view(()), lse, dq, flag
+
+
+def check_proto_nce_flag(flag):
+    """Reads the flag of a proto_nce call (one host synchronisation) and raises SsvError for what it reports."""
+    bits = 0 if flag is None else int(flag.item())
+    if bits & 1:
+        raise _lib.SsvError("proto_nce: a label lies outside its segment of prototypes")
+    if bits & 2:
+        raise _lib.SsvError("proto_nce: an inverse concentration is not finite and positive")
+
+
 # ------------------------------------------------------------------------------------------- ViT / DINO pieces
 LN_EPS = 1e-5
 ATTENTION_BF16X3 = True      # the attention forward's two products in the bf16x3 arithmetic when ops.ARITHMETIC says so (the backward stays on the fp32 instruction)

@@ -87,6 +87,36 @@ def kmeans(fvecs, k, niter=25, nredo=1, seed=1234, device=None):
     return best
 
 
+def cluster_concentration(dist, labels, counts, alpha=10.0, temperature=0.2):
+    """PCL's concentration phi [k] (Li et al., ICLR 2021, eq. 12 and the authors' run_kmeans), fp32 on the device, from what ops.kmeans_assign returns: dist [n]
+    squared distances, labels [n] int32, counts [k] int32.  Per cluster phi = mean over its members of sqrt(dist) / log(count + alpha); a cluster with at most one
+    member takes the largest phi of the others; phi is clipped to its 10th and 90th percentiles (linear interpolation, numpy.percentile's default) and scaled so
+    that its mean is ``temperature``.  The sums run in double in a fixed order - members sorted by (label, index), one running sum, differences at the cluster
+    boundaries - without atomics: equal inputs give equal bits.  No host synchronisation."""
+    if not (dist.is_cuda and labels.is_cuda and counts.is_cuda):
+        raise RuntimeError("cluster_concentration runs on the GPU; there is no CPU fallback")
+    n, k = dist.numel(), counts.numel()
+    if dist.dim() != 1 or labels.shape != (n,) or counts.dim() != 1 or k < 1 or n < 1:
+        raise ValueError(f"cluster_concentration: expected dist [n], labels [n] and counts [k], got {tuple(dist.shape)}, {tuple(labels.shape)}, {tuple(counts.shape)}")
+    if not (float(alpha) > 1.0 and float(temperature) > 0.0):
+        raise ValueError(f"cluster_concentration: need alpha > 1 and temperature > 0 (got {alpha}, {temperature})")
+    order = torch.sort(labels.to(torch.int64), stable=True).indices                     # members by (label, index)
+    run = torch.cumsum(dist.to(torch.float64).clamp_min(0.0).sqrt()[order], 0)             # one running sum in double
+    run = torch.cat([run.new_zeros(1), run])
+    cnt = counts.to(torch.int64)
+    ends = torch.cumsum(cnt, 0)
+    sums = run[ends] - run[ends - cnt]
+    cntd = cnt.to(torch.float64)
+    phi = sums / cntd.clamp_min(1.0) / torch.log(cntd + float(alpha))
+    many = cnt > 1
+    top = torch.where(many, phi, phi.new_full((), -1.0)).max()
+    top = torch.where(top >= 0, top, top.new_ones(()))                                   # no cluster with two members: every phi is equal
+    phi = torch.where(many, phi, top)
+    lo, hi = torch.quantile(phi, phi.new_tensor([0.1, 0.9]))
+    phi = torch.minimum(torch.maximum(phi, lo), hi)
+    return (phi * (float(temperature) / phi.mean())).to(torch.float32)
+
+
 def compute_cluster_accuracy(fvecs, targets, num_classes=None, niter=25, nredo=1, seed=1234, device=None):
     """Cluster accuracy after Hungarian matching: k-means with k = num_classes (default targets.max() + 1) on the GPU, the cluster x class vote table on the GPU
     (ops.cluster_votes), scipy's linear_sum_assignment(n - votes) as in hungarian_match, matched votes / n."""

@@ -501,6 +501,41 @@ class MocoLoss(nn.Module):
         return _MocoFn.apply(query, keys, memory_vectors, k, self.normalize, self.temperature)
 
 
+class _ProtoNceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query, protos, inv_phi, labels, seg_end, module):
+        # the prototypes carry no gradient: one call gives the loss and d loss / dq (csrc/protonce.hip); backward only scales, as in _MocoFn
+        d = query.shape[1]
+        qn, inv_q = ops.l2norm_fwd(query.detach().contiguous(), module.normalize)
+        loss, module.last_lse, dq, module.last_flag = ops.proto_nce(qn, protos, inv_phi, labels, seg_end)
+        ctx.saved = ops.l2norm_bwd(qn, inv_q, dq, d, module.normalize)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        return ops.scale_(ctx.saved, dloss.contiguous()), None, None, None, None, None
+
+
+class ProtoNceLoss(nn.Module):
+    """The ProtoNCE term of Prototypical Contrastive Learning (Li et al., ICLR 2021; not in the reference) without sampled negatives: the mean over the
+    clusterings ("segments" of ``protos`` [ktot, D], cut by the python ints ``seg_end``) of the cross-entropy of softmax((q . c_j) / phi_j) against the query's
+    own prototype, q the L2-normalised ``query`` [B, D], ``inv_phi`` [ktot] = 1 / phi, ``labels`` [segs, B] int32 indices inside each segment.  Gradients reach
+    ``query`` only.  D % 4 == 0 (a multiple of 32 up to 128 takes the fused kernel).  ``last_flag`` (device int32 [1]; ops.check_proto_nce_flag) and ``last_lse``
+    belong to the last forward: the flag is NOT read here - a trainer reads it once per epoch."""
+
+    def __init__(self, normalize=True):
+        super().__init__()
+        self.normalize = bool(normalize)
+        self.last_flag = self.last_lse = None
+
+    def forward(self, query, protos, inv_phi, labels, seg_end):
+        if query.dim() != 2 or protos.dim() != 2 or protos.shape[1] != query.shape[1] or query.shape[1] % 4 or query.shape[0] > _lib.PROTO_NCE_MAX_M:
+            raise ValueError(f"ProtoNceLoss needs query [B, D] and protos [ktot, D] with D % 4 == 0 and B <= {_lib.PROTO_NCE_MAX_M}, got {tuple(query.shape)} and {tuple(protos.shape)}")
+        if hdist.is_on():
+            raise NotImplementedError("ProtoNceLoss is single-process: the prototypes are not replicated across ranks")
+        return _ProtoNceFn.apply(query, protos, inv_phi, labels, tuple(int(e) for e in seg_end), self)
+
+
 class _PirlFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img_features, patch_features, bank, pos_index, neg_index, module):

@@ -26,6 +26,7 @@ CLASSES = (
     ("misc", "knn_select_k"), ("misc", "knn_merge_k"), ("misc", "knn_vote_k"), ("misc", "knn_flag_zero_k"),
     ("misc", "nn_prep_k"), ("misc", "nn_fused_k"), ("misc", "nn_rowarg_k"), ("misc", "nn_fold_k"),
     ("loss", "whiten_fwd_k"), ("loss", "whiten_bwd_k"), ("misc", "wmse_perm_k"), ("misc", "wmse_step_advance_k"),
+    ("loss", "pn_check_k"), ("loss", "pn_loss_k"), ("loss", "pn_prep_k"), ("loss", "pn_fused_k"), ("loss", "pn_fold_k"), ("loss", "pn_pad_k"), ("loss", "pn_row_k"),
 )
 CONV_FAMILY = ("conv_fwd", "conv_dgrad", "conv_wgrad")
 # host functions whose kernels run under another class's scope than the table gives them - both inside the conv family, so the family sums agree:
