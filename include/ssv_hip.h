@@ -553,9 +553,10 @@ int ssv_knn_label_agreement_arith(int64_t n, int32_t d, const float* z, const in
  * x [n][d] and centroids [k][d] fp32, dense; 1 <= k <= min(n, SSV_KMEANS_MAX_K), d % 4 == 0 (pad with zero columns: exact), d <= SSV_KMEANS_MAX_D, n <= 2^30;
  * anything else is refused, never clamped.
  * ssv_kmeans_assign: labels[i] = argmax_j (x_i . c_j - 1/2 |c_j|^2), exact ties to the lowest j (bit-identical centroid rows score bit-identically, so a duplicate
- * never wins against its first copy); dist[i] = max(0, |x_i|^2 + |c|^2 - 2 x_i . c) in fp32; counts[j] = rows labelled j; *objective = sum dist (per-row-block
+ * never wins against its first copy); dist[i] = |x_i - c_label|^2, summed directly over the columns in fp32 once the label is known (exactly 0 for a row that is its
+ * centroid; no cancellation of |x|^2 + |c|^2 against 2 x . c); counts[j] = rows labelled j; *objective = sum dist (per-row-block
  * partials folded in fixed order: equal inputs give equal bits).  SSV_ARITH_BF16X3: the search is fused into the X C^T product on v_mfma_f32_32x32x16_bf16 - the n x k
- * scores never reach memory, |x|^2 comes from the same pass, x is read once per block of 256 centroids.  SSV_ARITH_F32_MFMA: X C^T by row chunks through the
+ * scores never reach memory, x is read once per block of 256 centroids and once more for the distance.  SSV_ARITH_F32_MFMA: X C^T by row chunks through the
  * workspace (ssv_conv2d_fwd), then one wavefront per row.
  * prep: ssv_kmeans_prep_bytes(d, k) bytes the caller owns - 1/2 |c|^2 and the centroids' three bf16 planes in the fused kernel's operand order.  prep_ready == 0: the
  * call makes them from `centroids` first (once per call); != 0: they are what ssv_kmeans_update (or an earlier assignment of the SAME centroids) left there.
@@ -861,7 +862,9 @@ int ssv_queue_push_counted(int32_t K, int32_t D, float* bank, int32_t* ptr_dev, 
  * index inside the kernel and reduced on the fly: neither they nor any copy of bank rows reach memory.  K is cut into `splits` runs (0: the library's choice,
  * otherwise clamped to [1, min(64, tiles of 32 negatives)]); their partial (max, sum) pairs are folded in split order, so equal inputs give equal bits.
  * D must be a multiple of 4, at most 512; bank 16-byte aligned; ws 256-byte aligned, at least the workspace size for the LARGEST split count the call may
- * take (64 is always enough).  An index outside [0, N) is never dereferenced: the entry is left out and the first int32 of ws is set non-zero (0 otherwise). */
+ * take (64 is always enough).  An index outside [0, N) is never dereferenced and sets the first int32 of ws non-zero (0 otherwise): a negative outside the
+ * bank is left out of L_i; a POSITIVE outside it is not left out of the mean - its row is computed with m_i = 0 (all its logits 0, its two gradient rows 0), so
+ * the loss value is then meaningless, finite, and every other row's gradients are what they are with a valid index. */
 int64_t ssv_pirl_default_splits(int32_t B, int32_t K);
 size_t ssv_pirl_loss_workspace_bytes(int32_t B, int32_t splits);
 int ssv_pirl_loss_fwd_bwd(int64_t N, int32_t D, int32_t B, int32_t K, const float* bank, const void* pos_index, const void* neg_index,

@@ -1,14 +1,17 @@
 // Lloyd k-means on the GPU and the vote table of the Hungarian-matched cluster accuracy (the metric behind the reference's accuracy table: its README; the reference runs
 // faiss.Kmeans over encoder features at models/deep_cluster.py:100-118 and matches clusters to classes at utils/eval_utils.py:23-35, but never joins the two).
 //
-// Assignment.  label(i) = argmax_j (x_i . c_j - 1/2 |c_j|^2), exact ties to the LOWEST j; dist(i) = max(0, |x_i|^2 - 2 score) = max(0, |x_i|^2 + |c|^2 - 2 x_i . c).
+// Assignment.  label(i) = argmax_j (x_i . c_j - 1/2 |c_j|^2), exact ties to the LOWEST j; dist(i) = |x_i - c_label|^2, summed DIRECTLY over the columns once the
+//   label is known (one more read of the row and of one centroid row): |x|^2 - 2 score cancels |x|^2 + |c|^2 against 2 x . c, which left 2^-24 (|x|^2 + |c|^2) of
+//   one-sided noise (the clamp at 0) on every row that IS its centroid and a sum chain of d / 2 terms per lane (tests/test_gpu_kmeans_forms.py measured both).
 //   * SSV_ARITH_BF16X3: FUSED (kmeans_fused_k).  The n x k scores never reach memory.  A workgroup owns 128 rows (4 waves x 32) and walks d in chunks of 64; every
 //     lane loads ITS row's 8 floats of each 16-wide slab straight from HBM (row c = lane & 31, d = 16 s + 8 (lane >> 5) + 0..7: the B operand of
-//     v_mfma_f32_32x32x16_bf16, the layout of knn_fused_k's queries), splits them into the three bf16 planes in registers (csrc/split_bf16.h) and sums their squares
-//     on the way - |x|^2 comes from the same pass.  The centroids are split ONCE per call (kmeans_prep_k) into "fragment order": the 16 bytes lane l needs for
-//     (plane, slab, tile of 32 centroids) sit at ((plane * slabs + slab) * tiles + tile) * 64 + l, so a wave's A operand is one contiguous 1 KB load that stays in
-//     L2 / L1 (k <= 1024, d <= 2048: 12 MB at most).  Each (slab, tile) is six products, smallest terms first, into the tile's 32 x 32 accumulator; KT <= 8 tiles
-//     (256 centroids) are held at once, so x is read from HBM once for k <= 256 and once per block of 256 centroids beyond.
+//     v_mfma_f32_32x32x16_bf16, the layout of knn_fused_k's queries), splits them into the three bf16 planes in registers (csrc/split_bf16.h).  The centroids are split ONCE per
+//     call (kmeans_prep_k) into "fragment order": the 16 bytes lane l needs for (plane, slab, tile of 32 centroids) sit at
+//     ((plane * slabs + slab) * tiles + tile) * 64 + l, so a wave's A operand is one contiguous 1 KB load.  The planes take 6 d k bytes: 12 MB at k = 1024,
+//     d = 2048, which every row block finds in L2 / L1; up to the limits (k 4096, d 8192: 192 MB) the indexing is the same and only the reuse is lost - every
+//     row block then streams its planes from HBM, correct but slower.  Each (slab, tile) is six products, smallest terms first, into the tile's 32 x 32
+//     accumulator; KT <= 8 tiles (256 centroids) are held at once, so x is read from HBM once for k <= 256 and once per block of 256 centroids beyond.
 //     The arg-max is ONE compare-select per accumulator element after the last slab (lane (c, h) holds row c's scores of centroids (r & 3) + 8 (r >> 2) + 4 h of
 //     each tile, ascending in r: a strict > keeps the lowest index) and one exchange with the partner lane per ROW BLOCK - the vector pipe does not hide behind
 //     the matrix pipe (profiles/r02_probe_mfma_plus_valu.txt), so there is nothing per slab.
@@ -93,7 +96,7 @@ __device__ __forceinline__ void block_tail(bool owner, int slot, int label, floa
 
 template <int KT>
 __global__ void __launch_bounds__(256, KT >= 4 ? 1 : 2)
-kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, const u32x4* __restrict__ planes, const float* __restrict__ hc,
+kmeans_fused_k(const float* __restrict__ x, const float* __restrict__ cent, int n, int d, int k, int T, int S4, const u32x4* __restrict__ planes, const float* __restrict__ hc,
                int32_t* __restrict__ labels, float* __restrict__ dist, int32_t* __restrict__ counts, float* __restrict__ partial) {
   __shared__ float sd[128];
   __shared__ int hist[HIST];
@@ -111,7 +114,7 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
       r[i] = col < d ? *(const f32x4*)(xp + 64 * ch + 16 * (i >> 1) + 4 * (i & 1)) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   };
-  float best = -INFINITY, xx = 0.f;
+  float best = -INFINITY;
   int bi = 0;
   for (int tb = 0; tb < T; tb += KT) {                                  // one pass over x per block of KT tiles
     f32x16 acc[KT];
@@ -131,7 +134,6 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
       for (int q = 0; q < 3; ++q) kf[st][q] = frag(st / KT, st % KT, q);
     f32x4 xr[8];
     load_x(0, xr);
-    float ss = 0.f;
     for (int ch = 0; ch < nch; ++ch) {
       f32x4 xn[8];
       load_x(min(ch + 1, nch - 1), xn);                                 // the last chunk is loaded twice rather than branching around the prefetch
@@ -140,10 +142,6 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
       for (int sl = 0; sl < 4; ++sl) {
         bf16x8 xb[3];
         splitbf::split8(xr[2 * sl], xr[2 * sl + 1], xb);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss = __builtin_fmaf(xr[2 * sl][e], xr[2 * sl][e], ss);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss = __builtin_fmaf(xr[2 * sl + 1][e], xr[2 * sl + 1][e], ss);
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
           const int st = sl * KT + t, nx = st + NB - 1;                  // compile-time after unrolling
@@ -156,7 +154,6 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
 #pragma unroll
       for (int i = 0; i < 8; ++i) xr[i] = xn[i];
     }
-    if (tb == 0) xx = ss + __shfl_xor(ss, 32, 64);                      // the row's two halves; a + b in one lane, b + a in the other: the same float
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       if (tb + t < T) {
@@ -176,7 +173,30 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
     }
   }
   SSV_ARGMAX_FIRST_STEP(best, bi, 32);                                     // the row's other half
-  const float dd = fmaxf(0.f, __builtin_fmaf(-2.f, best, xx));
+  // the distance to the winner (both halves hold the same bi < k): this half's columns, chunk by chunk - no chain longer than 32 + d / 64 additions
+  const float* xq = x + (int64_t)min(row, n - 1) * d;
+  const float* cq = cent + (int64_t)bi * d;
+  float dsum = 0.f;
+#pragma unroll 2
+  for (int ch = 0; ch < nch; ++ch) {
+    f32x4 xv[8], cv[8];
+    bool in[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                                        // all sixteen loads before the first use; a float4 behind the row re-reads the row's start instead
+      const int col = 64 * ch + 16 * (i >> 1) + 8 * half + 4 * (i & 1);
+      in[i] = col < d;                                                   // d % 4 == 0: a float4 is inside the row or behind it
+      const int o = in[i] ? col : 0;
+      xv[i] = *(const f32x4*)(xq + o);
+      cv[i] = *(const f32x4*)(cq + o);
+    }
+    float part = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float df = in[i] ? xv[i][e] - cv[i][e] : 0.f; part = __builtin_fmaf(df, df, part); }
+    dsum += part;
+  }
+  const float dd = dsum + __shfl_xor(dsum, 32, 64);                       // a + b in one lane, b + a in the other: the same float
   const bool owner = half == 0 && row < n;
   if (owner) { labels[row] = bi; dist[row] = dd; }
   __syncthreads();                                                      // hist is zero everywhere
@@ -184,7 +204,7 @@ kmeans_fused_k(const float* __restrict__ x, int n, int d, int k, int T, int S4, 
 }
 
 // the unfused route: one wavefront per row of S [rows][k] (chunk of rows from row0), 4 rows per workgroup
-__global__ void __launch_bounds__(256) kmeans_rowarg_k(const float* __restrict__ S, int rows, int row0, int d, int k, const float* __restrict__ x, const float* __restrict__ hc,
+__global__ void __launch_bounds__(256) kmeans_rowarg_k(const float* __restrict__ S, int rows, int row0, int d, int k, const float* __restrict__ x, const float* __restrict__ cent, const float* __restrict__ hc,
                                                        int32_t* __restrict__ labels, float* __restrict__ dist, int32_t* __restrict__ counts, float* __restrict__ partial) {
   __shared__ float sd[4];
   __shared__ int hist[HIST];
@@ -204,14 +224,14 @@ __global__ void __launch_bounds__(256) kmeans_rowarg_k(const float* __restrict__
   }
   SSV_WAVE_ARGMAX_FIRST(best, bi);
   const float* xp = x + (int64_t)(row0 + rr) * d;
+  const float* cp = cent + (int64_t)bi * d;                              // every lane holds the same bi < k
   float ss = 0.f;
   for (int e = lane * 4; e < d; e += 256) {
-    const f32x4 v = *(const f32x4*)(xp + e);
+    const f32x4 v = *(const f32x4*)(xp + e), w = *(const f32x4*)(cp + e);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) ss = __builtin_fmaf(v[q], v[q], ss);
+    for (int q = 0; q < 4; ++q) { const float df = v[q] - w[q]; ss = __builtin_fmaf(df, df, ss); }
   }
-  ss = wave_sum(ss);
-  const float dd = fmaxf(0.f, __builtin_fmaf(-2.f, best, ss));
+  const float dd = wave_sum(ss);
   const bool owner = live && lane == 0;
   if (owner) { labels[row0 + r] = bi; dist[row0 + r] = dd; }
   block_tail<4>(owner, lane == 0 ? wave : -1, bi, dd, k, counts, partial + row0 / 4, sd, hist);
@@ -331,7 +351,7 @@ extern "C" int ssv_kmeans_assign(int64_t n, int32_t d, int32_t k, const float* x
     const u32x4* planes = (const u32x4*)((const char*)prep + g.hc_bytes);
     np = (int)cdiv64(n, 128);
     const dim3 grid((unsigned)np);
-#define SSV_KM(KT) hipLaunchKernelGGL(kmeans_fused_k<KT>, grid, dim3(256), 0, s, x, (int)n, d, k, g.T, g.S4, planes, hc, labels, dist, counts, partial)
+#define SSV_KM(KT) hipLaunchKernelGGL(kmeans_fused_k<KT>, grid, dim3(256), 0, s, x, centroids, (int)n, d, k, g.T, g.S4, planes, hc, labels, dist, counts, partial)
     if (g.T == 1) SSV_KM(1); else if (g.T == 2) SSV_KM(2); else if (g.T <= 4) SSV_KM(4); else SSV_KM(8);
 #undef SSV_KM
     SSV_CHECK_LAUNCH("kmeans_fused_k");
@@ -344,7 +364,7 @@ extern "C" int ssv_kmeans_assign(int64_t n, int32_t d, int32_t k, const float* x
       ssv_conv_desc cd = gemm_conv_desc(rows, d, k, SSV_ARITH_F32_MFMA);
       if (int rc = ssv_conv2d_fwd(&cd, x + r0 * d, centroids, nullptr, nullptr, S, stream)) return rc;         // S[rows, k] = X[r0 : r0 + rows] C^T
       ProfScope ps(SSV_PROF_MISC, s);
-      hipLaunchKernelGGL(kmeans_rowarg_k, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, (const float*)S, rows, (int)r0, d, k, x, hc, labels, dist, counts, partial);
+      hipLaunchKernelGGL(kmeans_rowarg_k, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, (const float*)S, rows, (int)r0, d, k, x, centroids, hc, labels, dist, counts, partial);
       SSV_CHECK_LAUNCH("kmeans_rowarg_k");
     }
   }

@@ -16,6 +16,12 @@ ASSIGN_CASES = ((389, 32, 10, 1.0), (1000, 96, 33, 2.0), (2048, 512, 100, 3.0), 
 PATH_CASES = ((5000, 16, 4096, 1.0),        # k > 1024: counts go straight to the global counters, 16 passes of 256 centroids in the fused kernel, two one-hot chunks in the update
               (4226, 24, 40, 2.0))          # n > 4096: two row chunks of the unfused product, the last one short
 ALL_CASES = ASSIGN_CASES + PATH_CASES
+# the launch forms of tests/test_gpu_kmeans_forms.py (its docstring says which branch each one reaches); tests/test_kmeans_cpu.py proves in fp64 that they stay under
+# the same near-tie cap and that every centroid of every set wins a row
+FORM_CASES = ((257, 64, 1, 1.0), (300, 32, 31, 1.0), (300, 32, 32, 1.0), (400, 64, 64, 2.0), (500, 68, 70, 2.0), (700, 60, 130, 2.0), (900, 128, 200, 2.0),
+              (1500, 128, 250, 2.0), (1200, 16, 257, 1.0), (1500, 48, 300, 2.0), (2000, 128, 500, 3.0), (3000, 128, 1000, 3.0), (1100, 16, 1024, 1.0),
+              (1100, 16, 1025, 1.0), (130, 8192, 3, 4.0), (200, 4096, 40, 4.0), (129, 4, 5, 1.0), (127, 36, 9, 1.0), (128, 36, 9, 1.0), (4097, 16, 7, 1.0),
+              (8195, 16, 4096, 1.0), (1, 4, 1, 1.0))
 EXCUSE = 2.0 ** -14                         # tau_i = EXCUSE * (|x_i|^2 + max_j |c_j|^2): the margin under which an fp32 assignment may differ from the fp64 one
 MAX_EXCUSED = 0.01
 
@@ -103,14 +109,31 @@ def margins(x, c):
 def assign_case(index):
     """(x float32 [n, d], [c0, c1, c2] float32): the case's blobs and its three centroid sets - the initial rows, then one and two oracle updates, rounded to
     float32 (the values both the GPU and the fp64 reference are given)."""
-    n, d, k, spread = ALL_CASES[index]
-    x, _ = blobs(100 + index, n, d, k, spread)
-    c = x[init_rows(200 + index, n, k)].astype(np.float64)
+    return _case(ALL_CASES[index], 100 + index, 200 + index)
+
+
+@functools.lru_cache(maxsize=None)
+def form_case(index):
+    """assign_case over FORM_CASES: blobs(300 + index, ...), init_rows(400 + index, ...)."""
+    return _case(FORM_CASES[index], 300 + index, 400 + index)
+
+
+def _case(case, blob_seed, init_seed):
+    n, d, k, spread = case
+    x, _ = blobs(blob_seed, n, d, k, spread)
+    c = x[init_rows(init_seed, n, k)].astype(np.float64)
     sets = [c.astype(np.float32)]
     for _ in range(2):
         c = update(x, assign(x, sets[-1])[0], sets[-1])
         sets.append(c.astype(np.float32))
     return x, sets
+
+
+def dist_at(x, c, labels, dtype):
+    """[n] squared distances to the centroids `labels` names, |x|^2 + |c_l|^2 - 2 x . c_l, every line in `dtype`: the reference of the accuracy rule of
+    tests/test_gpu_kmeans_forms.py in float64 and the SAME lines in float32."""
+    x, cl = np.asarray(x, dtype), np.asarray(c, dtype)[labels]
+    return (x * x).sum(1) + (cl * cl).sum(1) - dtype(2.0) * (x * cl).sum(1)
 
 
 def update_bound(x, labels, k):

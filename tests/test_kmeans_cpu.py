@@ -87,11 +87,93 @@ def test_new_entry_points_are_bound_and_declared():
     assert all(hasattr(eval_utils, f) for f in ("kmeans", "compute_cluster_accuracy"))
 
 
-@pytest.mark.parametrize("index", range(len(ko.ALL_CASES)))
-def test_assignment_cases_are_not_near_ties(index):
-    """The share of rows the GPU test may excuse (fp64 margin below tau_i), per centroid set, computed in fp64 alone: at most 1 %."""
-    x, sets = ko.assign_case(index)
+CASE_TABLE = [("assign", i) for i in range(len(ko.ALL_CASES))] + [("form", i) for i in range(len(ko.FORM_CASES))]
+
+
+@pytest.mark.parametrize("table,index", CASE_TABLE, ids=[str(i) if t == "assign" else f"form{i}" for t, i in CASE_TABLE])
+def test_assignment_cases_are_not_near_ties(table, index):
+    """The share of rows the GPU test may excuse (fp64 margin below tau_i), per centroid set, computed in fp64 alone: at most 1 %.  For the launch forms of
+    tests/test_gpu_kmeans_forms.py also: every centroid of every set wins at least one row in fp64, so a tile, a pass or a register position whose scores were
+    never read back would lose rows the reference gives it."""
+    x, sets = ko.assign_case(index) if table == "assign" else ko.form_case(index)
+    case = (ko.ALL_CASES if table == "assign" else ko.FORM_CASES)[index]
+    assert x.shape == case[:2] and all(c.shape == (case[2], case[1]) and c.dtype == np.float32 for c in sets) and len(sets) == 3
     for c in sets:
         _, margin, tau = ko.margins(x, c)
         share = float((margin < tau).mean())
-        assert share <= ko.MAX_EXCUSED, (ko.ALL_CASES[index], share)
+        assert share <= ko.MAX_EXCUSED, (case, share)
+        if table == "form":
+            wins = np.bincount(ko.assign(x, c)[0], minlength=case[2])
+            assert (wins > 0).all(), (case, np.nonzero(wins == 0)[0][:10])
+
+
+def test_form_cases_reach_the_branches_their_table_claims():
+    """The launch selection of csrc/kmeans.hip restated: tiles of 32 centroids, KT in {1, 2, 4, 8} by the tile count, passes of KT tiles, chunks of 64 columns, the
+    LDS histogram up to 1024 clusters, row chunks of 4096 on the unfused route, one-hot chunks of 2^24 / kp rows in the update."""
+    import test_gpu_kmeans_forms as forms
+    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "kmeans.hip")).read()
+    assert "constexpr int HIST = 1024;" in src and "return n < 4096 ? n : 4096;" in src and "(1ll << 24) / kp" in src
+    assert "if (g.T == 1) SSV_KM(1); else if (g.T == 2) SSV_KM(2); else if (g.T <= 4) SSV_KM(4); else SSV_KM(8);" in src
+    seen = set()
+    for n, d, k, _ in ko.FORM_CASES:
+        tiles = -(-k // 32)
+        kt = 1 if tiles == 1 else 2 if tiles == 2 else 4 if tiles <= 4 else 8
+        seen.add(("kt", kt))
+        seen.add(("ragged block", tiles % kt != 0))
+        seen.add(("passes > 1 and padded", tiles > kt and k % 32 != 0))
+        seen.add(("chunks", min(-(-d // 64), 3)))
+        seen.add(("hist", k <= 1024))
+        seen.add(("row chunks", -(-n // 4096) > 1))
+        seen.add(("onehot chunks", min(-(-n // max(1, min(n, (1 << 24) // ((k + 3) & ~3)))), 3)))
+    for want in [("kt", 1), ("kt", 2), ("kt", 4), ("kt", 8), ("ragged block", True), ("passes > 1 and padded", True), ("chunks", 1), ("chunks", 2), ("chunks", 3),
+                 ("hist", True), ("hist", False), ("row chunks", True), ("onehot chunks", 3)]:
+        assert want in seen, want
+    assert {k for _, _, k, _ in ko.FORM_CASES} >= {250, 500, 1000, 1024, 1025}
+    assert max(d for _, d, _, _ in ko.FORM_CASES) == forms.MAX_D == int(re.search(r"#define SSV_KMEANS_MAX_D\s+(\d+)", open(os.path.join(ROOT, "include", "ssv_hip.h")).read()).group(1))
+
+
+def test_case_table_covers_every_documented_branch():
+    """Every branch label of the docstring of tests/test_gpu_kmeans_forms.py is targeted by a test there, no test names an unknown label, the FORM_CASES rows of
+    the table are the oracle's, and the accuracy bound respects its caps."""
+    import math
+    import test_gpu_kmeans_forms as forms
+    doc = forms.documented_labels()
+    assert len(doc) >= 30
+    used = {b for labels in forms.TARGETS.values() for b in labels.split()}
+    assert not set(doc) - used, f"documented branches without a case: {sorted(set(doc) - used)}"
+    assert not used - set(doc), f"cases name undocumented branches: {sorted(used - set(doc))}"
+    tests = {name for name in dir(forms) if name.startswith("test_")}
+    assert set(forms.TARGETS) == tests, sorted(set(forms.TARGETS) ^ tests)
+    assert all(doc[b] in ("ssv_kmeans_assign", "ssv_kmeans_update", "ssv_cluster_votes") for b in doc)
+    rows = forms.documented_form_cases()
+    assert rows == {i: c for i, c in enumerate(ko.FORM_CASES)}
+    assert 1.0 <= forms.FACTOR <= 8.0 and math.log2(forms.FACTOR).is_integer() and 0.0 <= forms.FLOOR <= 16 * 2.0 ** -24
+
+
+def test_the_accuracy_bound_is_what_the_committed_report_implies():
+    """FACTOR = the worst measured ratio of profiles/kmeans_pirl_forms_report.json rounded up to the next power of two, never above 8; FLOOR as measured under."""
+    import json
+    import forms_report as fr
+    import test_gpu_kmeans_forms as forms
+    fam = json.load(open(os.path.join(ROOT, "profiles", "kmeans_pirl_forms_report.json")))["families"]["kmeans.dist"]
+    worst = max(fam["worst_e_ratio"], fam["worst_m_ratio"])
+    assert worst <= 8.0 and fam["FLOOR"] == forms.FLOOR and forms.FACTOR == fr.next_pow2(worst) == fam["FACTOR"]
+
+
+def test_the_distance_reference_is_well_conditioned():
+    """ref32 (tests/kmeans_oracle.py::dist_at in float32) within 1e-3 of ref64 (e and m) at the fp64 labels of every form case and set; the reference is
+    identically zero - the relative errors undefined - only where tests/test_gpu_kmeans_forms.py says so (n = k = 1: the row is its own centroid)."""
+    import test_gpu_kmeans_forms as forms
+    zero = set()
+    for index in range(len(ko.FORM_CASES)):
+        x, sets = ko.form_case(index)
+        for which, c in enumerate(sets):
+            labels = ko.assign(x, c)[0]
+            r64, r32 = ko.dist_at(x, c, labels, np.float64), ko.dist_at(x, c, labels, np.float32)
+            assert r64.dtype == np.float64 and r32.dtype == np.float32 and np.isfinite(r64).all()
+            if not np.abs(r64).max() > 0:
+                zero.add(index)
+                continue
+            e, m = forms.errors(r32, r64)
+            assert e <= 1e-3 and m <= 1e-3, (ko.FORM_CASES[index], which, e, m)
+    assert zero == set(forms.ZERO_REFERENCE)

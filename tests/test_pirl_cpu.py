@@ -98,6 +98,136 @@ def test_config_has_the_reference_keys():
     assert (size[0] // cfg["patch_size"]) * (size[1] // cfg["patch_size"]) == cfg["num_patches"]
 
 
+def _forms():
+    import test_gpu_pirl_forms as forms
+    return forms
+
+
+def test_case_table_covers_every_documented_branch():
+    """Every branch label of the docstring of tests/test_gpu_pirl_forms.py is targeted by a case of the entry point it documents, no case names an unknown label,
+    ids are unique, and the bounds respect their caps."""
+    import math
+    forms = _forms()
+    doc = forms.documented_labels()
+    assert len(doc) >= 22
+    used = {}
+    for c in forms.CASES:
+        used.update({b: "ssv_pirl_loss_fwd_bwd" for b in c.labels})
+    used.update({label: "ssv_bank_momentum_update" for label, _ in forms.BANK_CASES})
+    used.update({label: "ssv_patch_split" for label, _ in forms.PATCH_CASES})
+    assert not set(doc) - set(used), f"documented branches without a case: {sorted(set(doc) - set(used))}"
+    assert not set(used) - set(doc), f"cases name undocumented branches: {sorted(set(used) - set(doc))}"
+    assert all(doc[b] == entry for b, entry in used.items())
+    ids = [c.id for c in forms.CASES]
+    assert len(ids) == len(set(ids))
+    assert set(forms.FACTOR) == set(forms.FLOOR) == {"pirl.loss", "pirl.bank"}
+    assert all(1.0 <= f <= 8.0 and math.log2(f).is_integer() for f in forms.FACTOR.values()) and all(0.0 <= f <= 16 * 2.0 ** -24 for f in forms.FLOOR.values())
+
+
+def test_the_accuracy_bounds_are_what_the_committed_report_implies():
+    """FACTOR = the worst measured ratio of profiles/kmeans_pirl_forms_report.json rounded up to the next power of two, never above 8; FLOOR as measured under."""
+    import json
+    from forms_report import next_pow2
+    forms = _forms()
+    families = json.load(open(os.path.join(ROOT, "profiles", "kmeans_pirl_forms_report.json")))["families"]
+    for name in ("pirl.loss", "pirl.bank"):
+        worst = max(families[name]["worst_e_ratio"], families[name]["worst_m_ratio"])
+        assert worst <= 8.0 and families[name]["FLOOR"] == forms.FLOOR[name] and forms.FACTOR[name] == next_pow2(worst) == families[name]["FACTOR"], name
+
+
+def test_form_cases_reach_the_splits_and_widths_their_table_claims():
+    """The split plan of ssv_pirl_loss_fwd_bwd and the staged row stride of pirl_lse_k restated for the cases that name them."""
+    forms = _forms()
+    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "pirl.hip")).read()
+    assert "splits = std::max(1, std::min(std::min(splits, ntile), 64));" in src and "return w < 512 ? w + 4 : w;" in src
+    by = {}
+    for c in forms.CASES:
+        for b in c.labels:
+            by.setdefault(b, []).append(c)
+    plans = {b: [forms.plan(c.shape[2], c.splits) for c in by[b] if c.splits] for b in ("lse.split_ragged", "lse.split_thin", "lse.split_clamp", "lse.split_max")}
+    assert plans["lse.split_ragged"][0] == (10, 3, 4) and plans["lse.split_thin"] == [(10, 1, 10)] and plans["lse.split_clamp"] == [(3, 1, 3)]
+    assert plans["lse.split_max"] == [(66, 2, 33)]
+    assert all(c.splits == 0 for c in by["lse.split_default"]) and len(by["lse.split_default"]) >= 10
+    widths = sorted(c.shape[1] for c in by["lse.width"])
+    assert widths == [4, 8, 12, 36, 68, 128, 508, 512]
+    lda = lambda d: 8 * ((d + 7) // 8) + (4 if 8 * ((d + 7) // 8) < 512 else 0)
+    assert lda(508) == 512 and lda(512) == 512 and lda(128) == 132 and {d % 8 for d in widths} == {0, 4}
+    assert sorted(c.shape[2] for c in by["lse.k_edge"]) == [31, 32, 33] and sorted(c.shape[0] for c in by["lse.b_edge"]) == [1, 31, 32]
+    assert {c.weight for c in by["lse.weight_edge"]} == {0.0, 1.0}
+    assert all(c.normalize == (0,) and c.scale == 6.0 and c.temperature == 0.05 for c in by["lse.online_max"])
+    for c in by["lse.online_max"]:                                   # "logits of several hundred"
+        _, _, bank, pos, neg = forms.loss_inputs(c)
+        assert float((bank[pos] @ bank[neg].t()).abs().max()) / c.temperature > 200.0
+
+
+@pytest.mark.parametrize("position", range(len(_forms().CASES)), ids=lambda i: _forms().CASES[i].id)
+def test_forms_reference_is_well_conditioned(position):
+    """ref32 within 1e-3 of ref64 (e and m) and the fp64 loss finite, for every tensor of every loss case (a gradient under a zero weight is identically zero in
+    both); the out-of-range indices are where the table says."""
+    from forms_report import errors
+    forms = _forms()
+    case = forms.CASES[position]
+    inp = forms.loss_inputs(case)
+    b, d, k, n = case.shape
+    pos, neg = inp[3], inp[4]
+    outside = (neg < 0) | (neg >= n)
+    assert int(outside.sum()) == {None: 0, "pos": 0, "neg": 3, "tile": 34}[case.bad] and bool(((pos < 0) | (pos >= n)).any()) == (case.bad == "pos")
+    assert len(set(pos.tolist())) == b and neg.numel() == k
+    if case.bad == "tile":
+        assert bool(outside[32:64].all())
+    if case.bad == "pos":
+        return
+    for normalize in case.normalize:
+        r64, r32 = forms.loss_reference(case, inp, torch.float64, normalize), forms.loss_reference(case, inp, torch.float32, normalize)
+        assert bool(torch.isfinite(r64["loss"])) and r64["loss"].dtype == torch.float64 and r32["loss"].dtype == torch.float32
+        for name, t in r64.items():
+            assert bool(torch.isfinite(t).all()) and bool(torch.isfinite(r32[name]).all()), name
+            if not float(t.abs().max()) > 0:
+                assert case.weight in (0.0, 1.0) and not float(r32[name].abs().max()) > 0
+                continue
+            e, m = errors(r32[name], t)
+            print(f"{case.id} normalize {normalize} {name}: e(ref32) {e:.3e} m(ref32) {m:.3e}")
+            assert e <= forms.COND and m <= forms.COND, (name, e, m)
+
+
+def test_forms_bank_reference_is_well_conditioned():
+    from forms_report import errors
+    forms = _forms()
+    for position, (label, p) in enumerate(forms.BANK_CASES):
+        bank, index, z = forms.bank_inputs(position)
+        assert len(set(index.tolist())) == p["n"] and int(index.min()) >= 0 and int(index.max()) < p["N"]
+        r64, r32 = (forms.bank_reference(bank, index, z, p["m"], dt) for dt in (torch.float64, torch.float32))
+        e, m = errors(r32[index], r64[index])
+        assert bool(torch.isfinite(r64).all()) and float(r64[index].abs().max()) > 0 and e <= forms.COND and m <= forms.COND, (label, e, m)
+
+
+def test_masked_reference_is_the_loss_on_the_filtered_index_list():
+    """What lse.bad_neg / lse.bad_tile are held to: po.pirl_loss on the negatives that lie inside the bank - spelled out by hand here, and equal to masking the
+    out-of-range columns out of both soft-max denominators."""
+    forms = _forms()
+    for case in (c for c in forms.CASES if c.bad in ("neg", "tile")):
+        img, patch, bank, pos, neg = forms.loss_inputs(case)
+        n = bank.shape[0]
+        kept = [int(i) for i in neg.tolist() if 0 <= i < n]
+        assert len(kept) == (67 if case.bad == "neg" else 36)
+        for normalize in case.normalize:
+            got = forms.loss_reference(case, (img, patch, bank, pos, neg), torch.float64, normalize)
+            zi, zp = img.double().requires_grad_(), patch.double().requires_grad_()
+            rows = bank.double()
+            temperature, weight = 1.0 / forms._s(1.0 / case.temperature), forms._s(case.weight)
+            by_hand = po.pirl_loss(zi, zp, rows[pos], rows[torch.tensor(kept)], bool(normalize), temperature, weight)
+            by_hand.backward()
+            assert got["loss"].item() == by_hand.item() and torch.equal(got["d_img"], zi.grad) and torch.equal(got["d_patch"], zp.grad)
+            # the same with every column present and the out-of-range ones at -inf
+            vi, vp = (torch.nn.functional.normalize(t, dim=-1) if normalize else t for t in (img.double(), patch.double()))
+            m = rows[pos]
+            inside = (neg >= 0) & (neg < n)
+            logits = (m @ rows[neg.clamp(0, n - 1)].t() / temperature).masked_fill(~inside[None, :], float("-inf"))
+            terms = [torch.logsumexp(torch.cat((p, logits), 1), 1) - p[:, 0] for p in ((m * vp).sum(1, keepdim=True) / temperature, (m * vi).sum(1, keepdim=True) / temperature)]
+            masked = (weight * terms[0] + (1.0 - weight) * terms[1]).mean()
+            assert abs(masked.item() - by_hand.item()) <= 1e-12 * abs(by_hand.item())
+
+
 def test_pirl_loss_needs_the_gpu():
     from ssv_amd import _lib
     from ssv_amd.utils import losses

@@ -6,7 +6,7 @@ is a child process under its own time limit.
              timed region), torch.argmax over its rows, torch.bincount.  The baseline produces neither the distances nor the objective.
   iteration  one full Lloyd iteration: kmeans_assign on the operands the last update left + kmeans_update; baseline: the three calls above, then
              torch one_hot, ops.conv2d_wgrad for onehot^T X, a division by the counts.
-Shapes (n, d, k): (50000, 512, 10), (50000, 2048, 100), (200000, 128, 1024).  x_bytes_per_s: the bytes of x (read once for k <= 256) over the median, beside the
+Shapes (n, d, k): (50000, 512, 10), (50000, 2048, 100), (200000, 128, 1024).  x_bytes_per_s: the bytes of x (counted once; the kernel reads them once per 256 centroids and once more for the distances) over the median, beside the
 measured float4 copy rate of the chip, 6.29 TB/s.
     python tools/bench_kmeans.py [--out profiles/kmeans_bench.json]"""
 import argparse
