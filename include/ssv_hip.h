@@ -88,7 +88,16 @@ int ssv_group_extract(int32_t K, int32_t R, int32_t S, int32_t Cg, int32_t group
  * the ResNeXt bottlenecks): the kernels of ssv_conv2d_fwd / _dgrad / _wgrad, but every output-column tile contracts only over the channels of the
  * groups it falls into - exact (the skipped products are against zero weights) and C/64 (forward), K/64 (data gradient) times fewer k-tiles.
  * groups must divide C and K.  The stride-1 data gradient is ssv_conv2d_fwd_grouped on the transposed bank (ssv_filter_transpose), like the dense one.
- * ssv_conv2d_wgrad_grouped leaves the weight gradient in the bank's layout with ONLY the diagonal blocks defined (what ssv_group_extract reads). */
+ * ssv_conv2d_wgrad_grouped leaves the weight gradient in the bank's layout with ONLY the diagonal blocks defined (what ssv_group_extract reads).
+ * With accumulate = 1 the off-diagonal entries of dwd stay undefined too: prior + whatever the skipped tiles' workspace held, NaN if that was NaN.
+ * Arithmetic under SSV_ARITH_BF16X3: ssv_conv2d_fwd_grouped takes the bf16-piece forward kernel like ssv_conv2d_fwd (C % 32 == 0, K % 4 == 0, w_planes
+ * given; always on the 64-column tile), one or two accumulators by R * S * C; ssv_conv2d_dgrad_grouped runs on fp32 MFMA always (its 64-column tile has no
+ * bf16-piece variant; w_planes is ignored); ssv_conv2d_wgrad_grouped takes the bf16-piece kernel like ssv_conv2d_wgrad (C % 4 == 0, K % 4 == 0).
+ * ssv_conv_arithmetic(d, 0) and (d, 2) hold for the grouped forward and weight gradient; the grouped data gradient is fp32 MFMA whatever (d, 1) says.
+ * With fewer than 32 channels per group a 32-channel k-tile of the bank is mostly zeros: fp32 MFMA rounds only for its nonzero products, the one-accumulator
+ * bf16-piece forward six times per k-tile whatever it holds - measured against fp64 its error is 1.08-1.12x the fp32-MFMA kernel's at 4 channels per group,
+ * 0.81x at 24 and 2.04x on a depthwise bank (1 channel); 0.35-0.43x with two accumulators (R * S * C > 1152); all of it within 0.31 of 16 * 2^-24 * sum |x w|
+ * (tests/test_gpu_grouped_forms.py, profiles/grouped_forms_report.json). */
 int ssv_conv2d_fwd_grouped(const ssv_conv_desc* d, int32_t groups, const float* x, const float* wd, const float* bias, const float* addend,
                            float* y, void* stream);
 int ssv_conv2d_dgrad_grouped(const ssv_conv_desc* d, int32_t groups, const float* dy, const float* wd, const float* addend, float* dx, void* stream);

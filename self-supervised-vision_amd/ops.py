@@ -21,8 +21,9 @@ def _empty(shape, like):
 # HOW the GEMM-shaped launches multiply (include/ssv_hip.h: ssv_conv_desc.arithmetic; csrc/split_bf16.h).  "bf16x3" (default since round 6): every fp32 operand as three
 # bf16 pieces, six exact piece products per fp32 product, fp32 accumulation on the bf16 matrix pipe - fp32 in, fp32 out, error against fp64 at or below the fp32-MFMA
 # kernels' on every layer shape (tests/test_gpu_split.py).  "f32": v_mfma_f32_32x32x2_f32 on the fp32 operands, the arithmetic of rounds 1-5.
-# SSV_ARITHMETIC=f32|bf16x3; bench.py reports both in one line.  Launches without a bf16-piece kernel (image stem, strided data gradient, grouped banks) run on
-# fp32 MFMA either way.
+# SSV_ARITHMETIC=f32|bf16x3; bench.py reports both in one line.  Launches without a bf16-piece kernel (image stem, C % 32 != 0 forwards, the strided data
+# gradient below 128 input channels and on every grouped bank) run on fp32 MFMA either way.  A grouped bank's forward, its stride-1 data gradient (the forward kernel
+# on the transposed bank) and its weight gradient DO take the bf16-piece kernels (tests/test_gpu_grouped_forms.py, rule (c)).
 ARITHMETIC = os.environ.get("SSV_ARITHMETIC", "bf16x3")
 if ARITHMETIC not in ("bf16x3", "f32"):
     raise _lib.SsvError(f"SSV_ARITHMETIC must be bf16x3 or f32 (got {ARITHMETIC!r})")
