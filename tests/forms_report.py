@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE shared by tests/test_gpu_kmeans_forms.py and tests/test_gpu_pirl_forms.py: rule (a) of tests/test_gpu_loss_kernels.py for one family of
-outputs, guarded device buffers, and the report both files write into under SSV_KMEANS_PIRL_REPORT=<path> (profiles/kmeans_pirl_forms_report.json).
+outputs, guarded device buffers, and the report both files write into under SSV_KMEANS_PIRL_REPORT=<path> (profiles/kmeans_pirl_forms_report.json).  The
+nearest-neighbour lookup, ProtoNCE and whitening form tests share it too and write profiles/lookup_loss_forms_report.json under SSV_LOOKUP_LOSS_FORMS_REPORT.
 
 Rule (a): with ref64 the plain reference in float64, ref32 the SAME lines in float32, e(x) = ||x - ref64||_2 / ||ref64||_2 and m(x) = max|x - ref64| / max|ref64|,
     e(got) <= FACTOR * e(ref32) + FLOOR     and the same for m;
@@ -63,9 +64,10 @@ class Family:
         return out
 
 
-def write(families):
-    """Merge the families measured by this process into the report SSV_KMEANS_PIRL_REPORT names (the two test files write one file between them)."""
-    path = os.environ.get("SSV_KMEANS_PIRL_REPORT")
+def write(families, env="SSV_KMEANS_PIRL_REPORT", sha_key="ssv_source_sha16", extra=None):
+    """Merge the families measured by this process into the report the environment variable `env` names (the test files of one report write one file between
+    them; by default the k-means / PIRL one).  `extra`: further top-level entries, merged key by key."""
+    path = os.environ.get(env)
     if not path:
         return
     from ssv_amd import _lib
@@ -73,11 +75,14 @@ def write(families):
     if os.path.exists(path):
         with open(path) as fh:
             doc = json.load(fh)
-    doc["ssv_source_sha16"] = _lib.source_sha16()
+    doc[sha_key] = _lib.source_sha16()
     for fam in families:
         if fam.cases:
             doc["families"][fam.name] = fam.summary()
             doc["cases"][fam.name] = fam.cases
+    for key, value in (extra or {}).items():
+        if value:
+            doc.setdefault(key, {}).update(value)
     with open(path, "w") as fh:
         json.dump(doc, fh, indent=1, sort_keys=True)
 

@@ -31,6 +31,37 @@ LOOKUP_CASES = {f"{m}x{n}x{d}-{k}": LookupCase(m, n, d, k) for m, n, d in LOOKUP
 # gauss case, 0 of the clustered one have such a row; the ones taken have none)
 SEEDS = {"64x70000x128-gauss": 2, "64x70000x128-clustered": 1}
 
+# ---- the launch forms (tests/test_gpu_nn_lookup_forms.py): (m, n, d), the smallest shape that reaches each form of csrc/nnlookup.hip the table above leaves out
+FORM_BIG_N = (1 << 21) + 600                                             # above SSV_NN_LOOKUP_SLICE * SSV_NN_LOOKUP_MAX_SLICES rows a slice doubles
+FORM_LOOKUP_SHAPES = ((96, 600, 32),          # three query tiles: nn_fused_k<4> with the fourth tile repeated and unwritten
+                      (128, 1299, 96),        # four full tiles, three slices, d % 64 = 32
+                      (70, 300, 1024),        # the widest fused width: 16 chunk trips
+                      (40, 300, 36),          # d % 32 != 0: unfused in both arithmetics
+                      (40, 300, 1056),        # above the fused limit: unfused in both arithmetics
+                      (1030, 200, 32),        # 33 tiles: five blocks of 8, the last with one live tile
+                      (1030, 200, 36),        # two query chunks on the unfused route
+                      (8, FORM_BIG_N, 32))    # L = 1024: a wave's quarter is 256 rows
+FORM_LOOKUP_CASES = {f"{m}x{n}x{d}-{k}": LookupCase(m, n, d, k) for m, n, d in FORM_LOOKUP_SHAPES for k in KINDS if n < FORM_BIG_N or k == "gauss"}
+# case id -> seed offset, as SEEDS above: with 70 queries ONE row within tau of a tie is 1.4 % (offsets 0, 1 and 2 have one such row, 3 has none)
+FORM_SEEDS = {"70x300x1024-clustered": 3}
+SLICE, MAX_SLICES, FUSED_MAX_D, CHUNK_ROWS = 512, 4096, 1024, 1024       # SSV_NN_LOOKUP_SLICE, _MAX_SLICES, _FUSED_MAX_D; the unfused route's query chunk
+
+
+def lookup_plan(m, n, d, arith):
+    """The launch plan of ssv_nn_lookup restated (csrc/nnlookup.hip: make_plan and the dispatch): {"fused", "bytes"} and, fused, T (query tiles), KT (tiles of a
+    workgroup: the template argument), blocks, nch (64-column chunk trips), L (rows of a slice), P (slices); unfused, chunks (of queries) and parts (of the bank)."""
+    cdiv, up = lambda a, b: -(-a // b), lambda v: (v + 255) // 256 * 256
+    if arith == "bf16x3" and d % 32 == 0 and d <= FUSED_MAX_D:
+        t, nch = cdiv(m, 32), cdiv(d, 64)
+        kt = 1 if t == 1 else 2 if t == 2 else 4 if t <= 4 else 8
+        rows = SLICE * cdiv(cdiv(n, SLICE), MAX_SLICES)
+        p = cdiv(n, rows)
+        return {"fused": True, "T": t, "KT": kt, "blocks": cdiv(t, kt), "nch": nch, "L": rows, "P": p, "bytes": 2 * up(p * 32 * t * 4) + 3 * 4 * nch * t * 1024}
+    pc = cdiv(n, cdiv(n, min((1 << 26) // d, 65536)))
+    cr = min(m, CHUNK_ROWS)
+    return {"fused": False, "chunks": cdiv(m, cr), "parts": cdiv(n, pc), "bytes": 2 * up(m * 4) + up(cr * pc * 4)}
+
+
 # (B, D, n): the loss cases
 LOSS_SHAPES = ((8, 32, 16), (48, 96, 256), (130, 128, 1000))
 TEMPERATURES = (0.1, 0.5)
@@ -49,8 +80,11 @@ def _unit(x):
 def lookup_inputs(name):
     """(queries [m, d], bank [n, d]) float32 numpy, rows of unit length.  gauss: Gaussian directions.  clustered: 50 unit centres, every row a centre plus 0.05
     Gaussian noise per coordinate, normalised - queries and bank rows of one cluster are near neighbours of each other."""
-    c = LOOKUP_CASES[name]
-    g = torch.Generator().manual_seed(4000 + SEEDS.get(name, 0) + 31 * list(LOOKUP_CASES).index(name))
+    if name in LOOKUP_CASES:
+        c, seed = LOOKUP_CASES[name], 4000 + SEEDS.get(name, 0) + 31 * list(LOOKUP_CASES).index(name)
+    else:
+        c, seed = FORM_LOOKUP_CASES[name], 9000 + FORM_SEEDS.get(name, 0) + 31 * list(FORM_LOOKUP_CASES).index(name)
+    g = torch.Generator().manual_seed(seed)
     if c.kind == "gauss":
         q, b = torch.randn(c.m, c.d, generator=g, dtype=torch.float64), torch.randn(c.n, c.d, generator=g, dtype=torch.float64)
     else:

@@ -62,6 +62,42 @@ def cases():
     return out
 
 
+# ---- the launch forms (tests/test_gpu_proto_nce_forms.py): the smallest shapes that reach each form of csrc/protonce.hip the table above leaves out
+EIGHT = (1, 2, 31, 32, 33, 255, 256, 257)             # SSV_PROTO_NCE_MAX_SEGS segments: below, at and above a tile; below, at and above a slice
+LONG = 8200                                           # above SLICE * MAX_SLICES rows a slice doubles: 17 slices of 512, the last holding 8 rows
+FORM_CASES = [(1, 96, (33,), "plain"), (33, 96, (513,), "plain"), (70, 96, (7, 33, 600), "plain"), (70, 96, (513,), "dup"), (70, 96, (7, 33, 600), "late"),
+              (70, 160, (7, 33, 600), "plain"),
+              (70, 32, EIGHT, "plain"), (70, 36, EIGHT, "plain"),
+              (70, 64, (255,), "plain"), (70, 64, (256,), "plain"), (70, 64, (257,), "plain"),
+              (33, 32, (LONG,), "plain"), (33, 128, (LONG,), "late"),
+              (1030, 4, (7, 33), "plain"), (1030, 36, (7, 33), "plain"), (1030, 32, (7, 33), "plain")]
+FORM_ROUTES_AGREE = [(70, 96, (7, 33, 600), "plain"), (33, 128, (LONG,), "late")]
+FORM_SEEDS = (0, 1, 2)                                # the seeds tests/test_pcl_cpu.py checks the reference-side conditions at; the GPU runs seed 0
+MAX_SLICES, MAX_SEGS, CHUNK_ROWS = 32, 8, 1024        # SSV_PROTO_NCE_MAX_SLICES, SSV_PROTO_NCE_MAX_SEGS; the unfused route's query chunk
+
+
+def plan(m, d, sizes, arith):
+    """The launch plan of ssv_proto_nce restated (csrc/protonce.hip: make_plan, read_segments and the dispatch): {"fused", "bytes"} and, fused, DT and KT (the
+    template arguments), T (query tiles), blocks, rows / first (rows of one slice and first slice of every segment; first[-1] = all slices); unfused, cr (query rows
+    of a chunk), chunks and kp (rows of the padded copy of every segment)."""
+    cdiv, up = lambda a, b: -(-a // b), lambda v: (v + 255) // 256 * 256
+    segs, ktot = len(sizes), sum(sizes)
+    common = up(segs * cdiv(m, 32) * 32 * 4) + up(segs * m * 4)
+    if arith == "bf16x3" and d % 32 == 0 and d <= FUSED_MAX_D:
+        t, dt = cdiv(m, 32), d // 32
+        kt = 1 if t == 1 or dt >= 3 else 2
+        rows = [SLICE * cdiv(cdiv(k, SLICE), MAX_SLICES) for k in sizes]
+        first = [0]
+        for k, r in zip(sizes, rows):
+            first.append(first[-1] + cdiv(k, r))
+        worst = min(cdiv(ktot, SLICE) + segs, MAX_SLICES * segs)
+        return {"fused": True, "DT": dt, "KT": kt, "T": t, "blocks": cdiv(t, kt), "rows": rows, "first": first,
+                "bytes": common + 2 * up(4 * worst * 32 * t * 4) + up(4 * worst * 32 * t * d * 4) + 3 * (d // 16) * t * 1024}
+    longest = (ktot - (segs - 1) + 15) // 16 * 16
+    cr = max(1, min((1 << 25) // longest, CHUNK_ROWS, m))
+    return {"fused": False, "cr": cr, "chunks": cdiv(m, cr), "kp": [(k + 15) // 16 * 16 for k in sizes], "bytes": common + up(cr * longest * 4) + up(longest * d * 4)}
+
+
 def case_id(case):
     m, d, sizes, variant = case
     return f"m{m}-d{d}-k{'_'.join(map(str, sizes))}-{variant}"

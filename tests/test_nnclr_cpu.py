@@ -145,3 +145,103 @@ def test_near_ties_stay_under_the_cap(name):
     q, b = no.lookup_inputs(name)
     for x in (q, b):
         assert np.abs(np.sqrt((x.astype(np.float64) ** 2).sum(1)) - 1).max() < 1e-6
+
+
+# ---- the launch forms of tests/test_gpu_nn_lookup_forms.py ------------------------------------------------------------------------------------------------------
+ARITHS = ("bf16x3", "f32")
+
+
+def _code(arith):
+    from ssv_amd import _lib
+    return _lib.ARITH_BF16X3 if arith == "bf16x3" else _lib.ARITH_F32_MFMA
+
+
+def test_lookup_plan_restatement_is_the_librarys():
+    """nnclr_oracle.lookup_plan against what the library exposes of its plan: the workspace size in both arithmetics (slices x padded queries and the queries'
+    planes, or the chunk of S) and the rows of a slice, at every old and new case and at shapes around each threshold; and the dispatch line it restates."""
+    from ssv_amd import _lib, ops
+    assert (no.SLICE, no.MAX_SLICES, no.FUSED_MAX_D) == (_lib.NN_LOOKUP_SLICE, _lib.NN_LOOKUP_MAX_SLICES, _lib.NN_LOOKUP_FUSED_MAX_D)
+    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "nnlookup.hip")).read()
+    assert "if (p.T == 1) SSV_NN(1); else if (p.T == 2) SSV_NN(2); else if (p.T <= 4) SSV_NN(4); else SSV_NN(8);" in src
+    assert f"constexpr int CHUNK_ROWS = {no.CHUNK_ROWS};" in src and "PART_ELEMS = 1ll << 26, MAX_PART_COLS = 65536;" in src
+    lib = _lib.load()
+    s, cap = no.SLICE, no.SLICE * no.MAX_SLICES
+    shapes = list(no.LOOKUP_SHAPES + no.FORM_LOOKUP_SHAPES)
+    shapes += [(m, 700, 64) for m in (1, 32, 33, 64, 65, 96, 97, 128, 129, 8192)] + [(40, n, 32) for n in (1, s, s + 1, cap, cap + 1, 2 * cap, 2 * cap + 1)]
+    shapes += [(1025, 70000, d) for d in (4, 1020, 1024, 1028, 8192)]
+    for m, n, d in shapes:
+        for arith in ARITHS:
+            p = no.lookup_plan(m, n, d, arith)
+            assert lib.ssv_nn_lookup_workspace_bytes(m, n, d, _code(arith)) == p["bytes"], (m, n, d, arith)
+            assert p["fused"] == (arith == "bf16x3" and d % 32 == 0 and d <= no.FUSED_MAX_D)
+            if p["fused"]:
+                assert p["L"] == ops.nn_lookup_slice_rows(n) and (p["P"] - 1) * p["L"] < n <= p["P"] * p["L"] and p["P"] <= no.MAX_SLICES
+                assert p["KT"] in (1, 2, 4, 8) and (p["blocks"] - 1) * p["KT"] < p["T"] <= p["blocks"] * p["KT"]
+
+
+def test_form_cases_reach_every_launch_form():
+    """The forms the issue lists, from the restated plan: all four KT of nn_fused_k over the old and the new tables (the new one brings KT = 4, with T = 3 and with
+    T = 4), both routes under bf16x3 at d % 32 != 0 and at d > SSV_NN_LOOKUP_FUSED_MAX_D, nch = 16, L > SLICE, a ragged last block of KT = 8, two query chunks; and
+    every label of the GPU file is reached by the case that names it."""
+    import test_gpu_nn_lookup_forms as forms
+    new = [no.lookup_plan(m, n, d, "bf16x3") for m, n, d in no.FORM_LOOKUP_SHAPES]
+    old = [no.lookup_plan(m, n, d, "bf16x3") for m, n, d in no.LOOKUP_SHAPES]
+    assert {p["KT"] for p in old if p["fused"]} == {1, 2, 8}, "the table of tests/test_gpu_nnclr.py changed: revisit what the forms table must add"
+    assert {p["KT"] for p in new + old if p["fused"]} == {1, 2, 4, 8}
+    assert {p["T"] for p in new if p["fused"] and p["KT"] == 4} == {3, 4}
+    assert {p["fused"] for p in new} == {True, False}
+    unfused = [(m, n, d) for (m, n, d), p in zip(no.FORM_LOOKUP_SHAPES, new) if not p["fused"]]
+    assert any(d % 32 != 0 and d < no.FUSED_MAX_D for _, _, d in unfused) and any(d % 32 == 0 and d > no.FUSED_MAX_D for _, _, d in unfused)
+    assert max(p["nch"] for p in new if p["fused"]) == no.FUSED_MAX_D // 64 == 16 and max(p["nch"] for p in old) < 16
+    assert max(p["L"] for p in new if p["fused"]) == 2 * no.SLICE and all(p["L"] == no.SLICE for p in old)
+    assert any(p["fused"] and p["KT"] == 8 and p["T"] % 8 == 1 for p in new)
+    for arith in ARITHS:
+        assert any(no.lookup_plan(m, n, d, arith).get("chunks") == 2 for m, n, d in no.FORM_LOOKUP_SHAPES)
+        assert all(no.lookup_plan(m, n, d, arith).get("chunks", 1) == 1 for m, n, d in no.LOOKUP_SHAPES)
+    assert set(forms.CASE_LABELS) == {f"{m}x{n}x{d}" for m, n, d in no.FORM_LOOKUP_SHAPES}
+    for (m, n, d) in no.FORM_LOOKUP_SHAPES:
+        for arith, label in zip(forms.ARITHS, forms.CASE_LABELS[f"{m}x{n}x{d}"]):
+            assert not label or forms.reaches(label, m, n, d, arith), (m, n, d, arith, label)
+    assert forms.ARITHS == ARITHS
+    kinds = {(c.m, c.n, c.d): set() for c in no.FORM_LOOKUP_CASES.values()}
+    for c in no.FORM_LOOKUP_CASES.values():
+        kinds[(c.m, c.n, c.d)].add(c.kind)
+    assert all(k == ({"gauss"} if n == no.FORM_BIG_N else set(no.KINDS)) for (_, n, _), k in kinds.items()) and set(kinds) == set(no.FORM_LOOKUP_SHAPES)
+    assert not set(no.FORM_LOOKUP_CASES) & set(no.LOOKUP_CASES)
+
+
+def test_forms_table_covers_every_documented_branch():
+    import test_gpu_nn_lookup_forms as forms
+    doc = forms.documented_labels()
+    assert len(doc) >= 13 and set(doc.values()) == {"ssv_nn_lookup"}
+    used = {b for labels in forms.TARGETS.values() for b in labels.split()}
+    assert not set(doc) - used, f"documented branches without a case: {sorted(set(doc) - used)}"
+    assert not used - set(doc), f"cases name undocumented branches: {sorted(used - set(doc))}"
+    assert set(forms.TARGETS) == {name for name in dir(forms) if name.startswith("test_")}
+
+
+def test_the_committed_forms_report_holds_every_lookup_run():
+    """profiles/lookup_loss_forms_report.json, "lookup": every case in both arithmetics at both scales, and the planted case; no row off the fp64 arg-max beyond
+    the excused ones, sim within tau"""
+    import json
+    doc = json.load(open(os.path.join(ROOT, "profiles", "lookup_loss_forms_report.json")))
+    runs = doc["lookup"]
+    assert set(runs) == {f"{name}[{a}] scale {s}" for name in list(no.FORM_LOOKUP_CASES) + ["planted"] for a in ARITHS for s in (1, 10)}
+    for name, r in runs.items():
+        assert r["off_the_fp64_argmax"] <= r["excused"] <= no.MAX_EXCUSED * r["rows"] and r["worst_sim_error_over_tau"] <= 1.0, name
+    assert re.fullmatch(r"[0-9a-f]{16}", doc["source_sha16"])
+
+
+@pytest.mark.parametrize("name", list(no.FORM_LOOKUP_CASES))
+def test_form_cases_stay_under_the_near_tie_cap(name):
+    r = no.lookup_reference(name)
+    c = no.FORM_LOOKUP_CASES[name]
+    share = float(r["excused"].mean())
+    print(f"{name}: {100 * share:.2f} % of {c.m} queries within tau of a tie (smallest margin {r['margin'].min():.3g}, tau {r['tau'].max():.3g})")
+    assert r["s"].shape == (c.m, c.n) and np.isfinite(r["s"]).all()
+    assert share <= no.MAX_EXCUSED
+    if c.n == no.FORM_BIG_N:
+        assert not r["excused"].any(), "with 8 queries one excused row is 12.5 %"
+    q, b = no.lookup_inputs(name)
+    for x in (q, b):
+        assert np.abs(np.sqrt((x.astype(np.float64) ** 2).sum(1)) - 1).max() < 1e-6

@@ -183,3 +183,98 @@ def test_case_table_keeps_the_fp32_reference_meaningful(case):
     if case[3] == "late":                                                  # the largest score of every query is the last prototype's
         sc = (q.double() @ protos.double()[seg_end[-2]:].T) * inv_phi.double()[seg_end[-2]:]
         assert bool((sc.argmax(dim=1) == sc.shape[1] - 1).all())
+
+
+# ---- the launch forms of tests/test_gpu_proto_nce_forms.py ------------------------------------------------------------------------------------------------------
+ARITHS = ("bf16x3", "f32")
+
+
+def test_plan_restatement_is_the_librarys():
+    """pcl_oracle.plan against what the library exposes of its plan - the workspace size in both arithmetics - at every old and new case and at shapes around
+    each threshold; and the dispatch lines it restates."""
+    from ssv_amd import _lib
+    assert (po.SLICE, po.MAX_SLICES, po.MAX_SEGS, po.FUSED_MAX_D) == (_lib.PROTO_NCE_SLICE, _lib.PROTO_NCE_MAX_SLICES, _lib.PROTO_NCE_MAX_SEGS, _lib.PROTO_NCE_FUSED_MAX_D)
+    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "protonce.hip")).read()
+    assert "p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;" in src and f"constexpr int CHUNK_ROWS = {po.CHUNK_ROWS};" in src and "CHUNK_ELEMS = 1ll << 25;" in src
+    assert "if (p.DT == 4) SSV_PN(4, 1); else if (p.DT == 3) SSV_PN(3, 1);" in src
+    lib = _lib.load()
+    shapes = [c[:3] for c in po.cases() + po.FORM_CASES]
+    shapes += [(m, d, (300, 300)) for m in (1, 32, 33, 64, 65, 1024, 1025, 8192) for d in (32, 64, 96, 128, 132, 160, 4)]
+    shapes += [(40, 32, (k,)) for k in (po.SLICE * po.MAX_SLICES, po.SLICE * po.MAX_SLICES + 1, 1 << 20)] + [(2000, 36, (40000, 5))]
+    for m, d, sizes in shapes:
+        for arith in ARITHS:
+            code = _lib.ARITH_BF16X3 if arith == "bf16x3" else _lib.ARITH_F32_MFMA
+            p = po.plan(m, d, sizes, arith)
+            assert lib.ssv_proto_nce_workspace_bytes(m, sum(sizes), d, len(sizes), code) == p["bytes"], (m, d, sizes, arith)
+            assert p["fused"] == (arith == "bf16x3" and d % 32 == 0 and d <= po.FUSED_MAX_D)
+            if p["fused"]:
+                assert all(r % po.SLICE == 0 and -(-k // r) <= po.MAX_SLICES for k, r in zip(sizes, p["rows"])) and p["first"][-1] <= min(-(-sum(sizes) // po.SLICE) + len(sizes), po.MAX_SLICES * len(sizes))
+
+
+def test_form_cases_reach_every_launch_form():
+    """All the (DT, KT) instantiations the dispatch of ssv_proto_nce can launch - six: DT = 3 and 4 with one query tile, DT = 1 and 2 with one (T = 1) or two -
+    over the old and the new tables, the new one bringing (3, 1); a segment with L > SLICE; eight segments; two unfused chunks; the unfused route under bf16x3 at a
+    width that is a multiple of 32; and every label of the GPU file is reached by the case that names it."""
+    import test_gpu_proto_nce_forms as forms
+    inst = lambda cases: {(p["DT"], p["KT"]) for p in (po.plan(*c[:3], "bf16x3") for c in cases) if p["fused"]}
+    assert inst(po.cases()) == {(1, 1), (1, 2), (2, 1), (2, 2), (4, 1)}, "the table of tests/test_gpu_proto_nce.py changed: revisit what the forms table must add"
+    assert (3, 1) in inst(po.FORM_CASES) and inst(po.cases() + po.FORM_CASES) == {(1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (4, 1)}
+    new = [po.plan(*c[:3], "bf16x3") for c in po.FORM_CASES]
+    assert any(p["fused"] and max(p["rows"]) > po.SLICE for p in new) and all(max(po.plan(*c[:3], "bf16x3").get("rows", [0])) <= po.SLICE for c in po.cases())
+    assert max(len(c[2]) for c in po.FORM_CASES) == po.MAX_SEGS == 8 and max(len(c[2]) for c in po.cases()) == 3
+    assert any(not p["fused"] and c[1] % 32 == 0 for c, p in zip(po.FORM_CASES, new))
+    for arith in ARITHS:
+        assert any(po.plan(*c[:3], arith).get("chunks") == 2 for c in po.FORM_CASES) and all(po.plan(*c[:3], arith).get("chunks", 1) == 1 for c in po.cases())
+    assert any(not p["fused"] and p["chunks"] == 2 and p["kp"][0] == c[2][0] for c, p in zip(po.FORM_CASES, (po.plan(*c[:3], "f32") for c in po.FORM_CASES))) or \
+        any(k % 16 == 0 for c in po.FORM_CASES for k in c[2]), "k % 16 == 0: pn_pad_k without a pad row"
+    assert {c[2] for c in po.FORM_CASES} >= {(255,), (256,), (257,), po.EIGHT, (po.LONG,)} and {po.SLICE - 1, po.SLICE, po.SLICE + 1} <= set(po.EIGHT)
+    assert len(set(po.FORM_CASES)) == len(po.FORM_CASES) and not set(po.FORM_CASES) & set(po.cases()) and set(po.FORM_ROUTES_AGREE) <= set(po.FORM_CASES)
+    assert set(forms.CASE_LABELS) == set(po.FORM_CASES) and forms.ARITHS == ARITHS
+    for case, labels in forms.CASE_LABELS.items():
+        for arith, label in zip(ARITHS, labels):
+            assert not label or forms.reaches(label, case, arith), (case, arith, label)
+    doc = forms.documented_labels()
+    assert len(doc) >= 13 and set(doc.values()) == {"ssv_proto_nce"}
+    used = {b for labels in forms.TARGETS.values() for b in labels.split()}
+    assert not set(doc) - used, f"documented branches without a case: {sorted(set(doc) - used)}"
+    assert not used - set(doc), f"cases name undocumented branches: {sorted(used - set(doc))}"
+    assert set(forms.TARGETS) == {name for name in dir(forms) if name.startswith("test_")}
+
+
+@pytest.mark.parametrize("seed", po.FORM_SEEDS)
+@pytest.mark.parametrize("case", po.FORM_CASES, ids=po.case_id)
+def test_form_cases_keep_the_fp32_reference_meaningful(case, seed):
+    """In fp64: the mean probability of the positive is below 0.9 and no score leaves [-60, 60]; the fp32 evaluation of dq is within 7e-7 of it (e)"""
+    ins = po.make_case(case, seed)
+    q, protos, inv_phi, labels, seg_end = ins
+    m, d, sizes, variant = case
+    assert q.shape == (m, d) and protos.shape == (sum(sizes), d) and labels.shape == (len(sizes), m) and seg_end[-1] == sum(sizes)
+    for s, k in enumerate(sizes):
+        assert 0 <= int(labels[s].min()) and int(labels[s].max()) < k
+    ref, r32 = po.proto_nce(*ins), po.proto_nce(*ins, dtype=torch.float32)
+    e = po.errs(r32["dq"], ref["dq"])[0]
+    print(f"{po.case_id(case)} seed {seed}: pos {ref['pos']:.3g} smax {ref['smax']:.3g} e(ref32) of dq {e:.3g}")
+    assert ref["pos"] < 0.9, ref["pos"]
+    assert ref["smax"] <= 60.0, ref["smax"]
+    assert float(ref["dq"].abs().max()) > 0.0 and float(ref["loss"]) > 0.0
+    assert e <= 7e-7, e
+    if variant == "late":
+        sc = (q.double() @ protos.double()[seg_end[-2] if len(seg_end) > 1 else 0:].T) * inv_phi.double()[seg_end[-2] if len(seg_end) > 1 else 0:]
+        assert bool((sc.argmax(dim=1) == sc.shape[1] - 1).all())
+    if variant == "dup":
+        assert torch.equal(protos[255], protos[256]) and inv_phi[255] == inv_phi[256]
+
+
+def test_the_forms_accuracy_bound_is_what_the_committed_report_implies():
+    """FACTOR of tests/test_gpu_proto_nce_forms.py = the worst measured ratio of profiles/lookup_loss_forms_report.json rounded up to the next power of two, never
+    above 8; every case and both arithmetics are in the report; the older table's FACTOR is untouched."""
+    import json
+    import forms_report as fr
+    import test_gpu_proto_nce_forms as forms
+    doc = json.load(open(os.path.join(ROOT, "profiles", "lookup_loss_forms_report.json")))
+    fam = doc["families"]["proto_nce.forms"]
+    worst = max(fam["worst_e_ratio"], fam["worst_m_ratio"])
+    assert worst <= 8.0 and fam["FLOOR"] == forms.FLOOR == po.FLOOR and forms.FACTOR == fr.next_pow2(worst) == fam["FACTOR"]
+    assert set(doc["cases"]["proto_nce.forms"]) == {f"{po.case_id(c)}[{a}]" for c in po.FORM_CASES for a in ARITHS}
+    assert all(set(t) == {"loss", "lse", "dq"} for t in doc["cases"]["proto_nce.forms"].values()) and re.fullmatch(r"[0-9a-f]{16}", doc["source_sha16"])
+    assert po.FACTOR == 4.0

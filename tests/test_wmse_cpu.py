@@ -184,3 +184,83 @@ def test_workspace_sizing_and_null_refusals():
     assert lib.ssv_last_error().decode().startswith("ssv_wmse_perm:")
     for n, views, iters in ((1, 1, 1), (4097, 2, 1), (512, 0, 1), (512, 9, 1), (512, 2, 0), (512, 2, 17)):
         assert lib.ssv_wmse_perm(n, views, iters, 0, 0, None, None, None) == -1, (n, views, iters)
+
+
+# ---- the launch forms of tests/test_gpu_whiten_forms.py ---------------------------------------------------------------------------------------------------------
+FORM_RUNS = [(c, s) for c in wo.FORM_CASES for s in wo.SEEDS]
+SEVEN_FORMS = {(16384, 16), (65536, 16), (65536, 8), (65536, 4), (163840, 4), (163840, 2), (163840, 1)}
+
+
+def test_lds_layout_restatement():
+    """wmse_oracle.lds_layout is csrc/whiten.hip's: the library does not expose the tier arithmetic, so the restatement is held against the footprints worked out
+    by hand from the kernel's section list - B0 | B1 | Sd | xs | (gs) | mu | gb | part | dg - and against the source lines it restates."""
+    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "whiten.hip")).read()
+    assert "while (kp < 16 && 2 * kp * T <= NT) kp *= 2;" in src and "l.P = P > 16 ? 16 : P;" in src and "constexpr int FCH = 32, BCH = 16;" in src
+    assert "if ((need) <= 16384)" in src and "else if ((need) <= 65536)" in src and "kernel<163840>" in src
+    # d = 24: 2 x 24 x 25 x 4 (two matrices) + 24 x 24 x 8 (Sd, kp 16) + 32 x 25 x 4 (chunk) + 24 x 4 + 24 x 8 + 16 x 24 x 8 (16 row classes) + 24 x 4
+    assert 2 * 2400 + 4608 + 3200 + 96 + 192 + 3072 + 96 == 16064 == wo.lds_layout(24)["total"]
+    # d = 56: 2 x 56 x 57 x 4 + 56 x 56 x 8 (kp 4) + 32 x 57 x 4 + 56 x 4 + 56 x 8 + 16 x 56 x 8 + 56 x 4
+    assert 2 * 12768 + 25088 + 7296 + 224 + 448 + 7168 + 224 == 65984 == wo.lds_layout(56)["total"] == 65536 + 448
+    # d = 128: 2 x 128 x 129 x 4 + 0 (kp 1: no Sd) + 32 x 129 x 4 + 128 x 4 + 128 x 8 + 8 x 128 x 8 (8 row classes) + 128 x 4
+    assert 2 * 66048 + 16512 + 512 + 1024 + 8192 + 512 == 158848 == wo.lds_layout(128)["total"] <= 163840
+    table = {}
+    for d in range(4, 129, 4):
+        fwd, bwd = wo.lds_layout(d), wo.lds_layout(d, bwd=True)
+        assert fwd == bwd, "32 rows of one operand and 16 rows of two are the same bytes"
+        assert fwd["kp"] * (d // 4) ** 2 <= 1024 and fwd["P"] * d <= 1024 and fwd["total"] <= fwd["tier"]
+        table.setdefault((fwd["tier"], fwd["kp"]), []).append(d)
+    assert table == {(16384, 16): [4, 8, 12, 16, 20, 24], (65536, 16): [28, 32], (65536, 8): [36, 40, 44], (65536, 4): [48, 52], (163840, 4): [56, 60, 64],
+                     (163840, 2): list(range(68, 89, 4)), (163840, 1): list(range(92, 129, 4))}
+    assert set(table) == SEVEN_FORMS
+    assert wo.lds_layout(88)["total"] == max(wo.lds_layout(d)["total"] for d in range(4, 129, 4) if wo.lds_layout(d)["kp"] > 1)
+    assert [wo.lds_layout(d)["P"] for d in (64, 68, 88, 92, 124, 128)] == [16, 15, 11, 11, 8, 8]
+
+
+def test_form_cases_reach_every_launch_form():
+    import test_gpu_whiten_forms as forms
+    form = lambda cases: {(wo.lds_layout(d)["tier"], wo.lds_layout(d)["kp"]) for _, _, d in cases}
+    assert form(wo.CASES) == {(16384, 16), (65536, 8), (163840, 4), (163840, 1)}, "the table of tests/test_gpu_wmse.py changed: revisit what the forms table must add"
+    assert form(wo.FORM_CASES) == SEVEN_FORMS == set(forms.FORM_OF_LABEL.values())
+    ds = {d for _, _, d in wo.FORM_CASES}
+    assert {24, 28, 52, 56, 44, 88} <= ds, "both tier boundaries from both sides, the upper edge of kp 8, the largest footprint with Sd"
+    assert {wo.lds_layout(d)["P"] for d in ds} >= {16, 15, 11, 8} and {wo.lds_layout(d)["P"] for _, _, d in wo.CASES} == {16, 8}
+    ws = [w for _, w, _ in wo.FORM_CASES]
+    assert {w % 4 for w in ws} == {0, 1, 2, 3} and all(w % 8 == 0 for _, w, _ in wo.CASES)
+    assert {1, 2, 3} <= {w % 16 for w in ws} and 3 in {w % 32 for w in ws} and 1024 in ws and any(w < 16 for w in ws)
+    assert all(w > d and w <= 1024 and d % 4 == 0 for _, w, d in wo.FORM_CASES) and not set(wo.FORM_CASES) & set(wo.CASES) and len(set(wo.FORM_CASES)) == len(wo.FORM_CASES)
+    rows = forms.documented_form_cases()
+    assert sorted(c for cs in rows.values() for c in cs) == sorted(wo.FORM_CASES)
+    for label, cases in rows.items():
+        assert all(forms.form_label(d) == label for _, _, d in cases), label
+    doc = forms.documented_labels()
+    assert len(doc) >= 13 and set(doc.values()) == {"ssv_whiten_fwd", "ssv_whiten_bwd"}
+    used = {b for labels in forms.TARGETS.values() for b in labels.split()}
+    assert not set(doc) - used, f"documented branches without a case: {sorted(set(doc) - used)}"
+    assert not used - set(doc), f"cases name undocumented branches: {sorted(used - set(doc))}"
+    assert set(forms.TARGETS) == {name for name in dir(forms) if name.startswith("test_")}
+
+
+def test_the_forms_accuracy_bound_is_what_the_committed_report_implies():
+    """FACTOR of tests/test_gpu_whiten_forms.py = the worst measured ratio of profiles/lookup_loss_forms_report.json rounded up to the next power of two, never
+    above 8; every case, seed and eps is in the report."""
+    import json
+    import forms_report as fr
+    import test_gpu_whiten_forms as forms
+    doc = json.load(open(os.path.join(ROOT, "profiles", "lookup_loss_forms_report.json")))
+    fam = doc["families"]["whiten.forms"]
+    worst = max(fam["worst_e_ratio"], fam["worst_m_ratio"])
+    assert worst <= 8.0 and fam["FLOOR"] == forms.FLOOR == 2 * 2.0 ** -24 and forms.FACTOR == fr.next_pow2(worst) == fam["FACTOR"]
+    want = {f"{b}x{w}x{d}-s{s}-eps{e:g}": {"y", "mean", "winv", "dx"} | ({"cov"} if e == 0.0 else set()) for b, w, d in wo.FORM_CASES for s in wo.SEEDS for e in wo.EPSES}
+    assert {k: set(t) for k, t in doc["cases"]["whiten.forms"].items()} == want and re.fullmatch(r"[0-9a-f]{16}", doc["source_sha16"])
+
+
+@pytest.mark.parametrize("case,seed", FORM_RUNS)
+def test_every_form_case_is_well_conditioned(case, seed):
+    x, rows, blocks = _blocks(case, seed)
+    assert x.dtype == torch.float32 and sorted(rows.flatten().tolist()) == list(range(x.shape[0]))
+    worst = 0.0
+    for xb in blocks:
+        xc = xb - xb.mean(dim=0)
+        worst = max(worst, float(torch.linalg.cond(xc.T @ xc / (xb.shape[0] - 1))))
+    print(f"{case} seed {seed}: worst cond(S) {worst:.3g}")
+    assert worst <= COND_MAX

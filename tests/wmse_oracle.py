@@ -8,11 +8,29 @@ import torch
 
 # (blocks, w, d): the smallest shape, a width that is no multiple of 32, w barely above d, the CIFAR configuration, the widest
 CASES = [(2, 8, 4), (5, 24, 12), (3, 40, 36), (4, 128, 64), (1, 136, 128), (2, 256, 128)]
+# the launch forms (tests/test_gpu_whiten_forms.py): every (LDS tier, k-split) form of csrc/whiten.hip's lds_layout, both tier boundaries, row-class counts that are
+# no power of two, and row counts that are no multiple of the 4 (forward) or 2 (backward) rows a thread owns
+FORM_CASES = [(3, 9, 4), (2, 7, 4), (2, 29, 24), (2, 37, 28), (2, 45, 36), (2, 50, 44), (2, 53, 48), (2, 61, 52), (2, 67, 56), (2, 81, 68), (2, 99, 88), (1, 101, 88),
+              (1, 103, 92), (1, 150, 124), (1, 1021, 128), (1, 1024, 128), (2, 1023, 8)]
 SEEDS = (0, 1, 2)
 EPSES = (0.0, 1e-3)
 # (blocks, w, d) that ssv_whiten_workspace_bytes / _fwd / _bwd refuse: no block, d = 0 / below 4 / no multiple of 4 / above 128, w = d, w < d, w above 1024, blocks * w >= 2^31, negative
 REFUSED_SHAPES = [(0, 128, 64), (8, 128, 0), (8, 128, 2), (8, 128, 66), (8, 256, 132), (8, 64, 64), (8, 32, 64), (8, 1025, 64), (1 << 22, 1024, 64), (-1, 128, 64)]
 PERM_VIEW_BASE = 2048        # the Philox view key of iteration t is PERM_VIEW_BASE + t (the augmentation streams use 0 .. 1024 + views)
+
+
+def lds_layout(d, bwd=False):
+    """csrc/whiten.hip's lds_layout restated: {"kp" (k-split of the d x d products), "P" (row classes of the column means), "total" (bytes of LDS), "tier" (the
+    instantiation that holds it)}.  The forward stages 32 rows of one operand, the backward 16 rows of two: the same bytes."""
+    ld, tiles, threads = d + 1, (d // 4) ** 2, 1024
+    kp = 1
+    while kp < 16 and 2 * kp * tiles <= threads:
+        kp *= 2
+    p = min(16, threads // d)
+    r16 = lambda v: (v + 15) // 16 * 16
+    mat, chunk = r16(d * ld * 4), r16((16 if bwd else 32) * ld * 4)
+    total = 2 * mat + (d * d * 8 if kp > 1 else 0) + chunk * (2 if bwd else 1) + d * 4 + d * 8 + p * d * 8 + d * 4
+    return {"kp": kp, "P": p, "total": total, "tier": 16384 if total <= 16384 else 65536 if total <= 65536 else 163840}
 
 
 def make_case(blocks, w, d, seed):
