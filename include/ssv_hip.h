@@ -745,6 +745,65 @@ size_t ssv_proto_nce_workspace_bytes(int32_t m, int64_t ktot, int32_t d, int32_t
 int ssv_proto_nce(int32_t m, int32_t d, int32_t segs, const int64_t* seg_end, const float* q, const float* protos, const float* inv_phi, const int32_t* labels,
                   float* loss, float* lse, float* dq, int32_t* flag, int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- DenseCL's dense term (csrc/densecl.hip; Wang, Zhang, Shen, Kong, Li, CVPR 2021).  The reference has no such trainer.  All matrices are dense row-major fp32.
+ * ssv_dense_match: the correspondence between the two views, from backbone features.  f1, f2 [b][s][c] - the NHWC feature map of an image viewed as s rows of c
+ *   channels, no transpose.  For image n and cell i of view 1:
+ *       j* = argmax_j (f1[n][i] . f2[n][j]) / max(|f2[n][j]|, eps)     the lowest j among equal scores; |f1| is a positive factor and cannot change the arg-max
+ *       idx[n][i] = n * s + j*     (a row of the [b * s][d] key grid: it feeds ssv_queue_nce as pos)        sim[n][i] = the cosine, both norms clamped by eps
+ *   An all-zero f1 row scores 0 everywhere and picks j = 0; an all-zero f2 row scores 0 and is never chosen over a positive score.  A cell whose scores are all
+ *   NaN gets j = 0 and sim = NaN.
+ *   arithmetic  the product runs in the call's arithmetic: SSV_ARITH_BF16X3 (the six-product accumulation of csrc/split_bf16.h on v_mfma_f32_32x32x16_bf16) or
+ *          SSV_ARITH_F32_MFMA (v_mfma_f32_32x32x2_f32); the norms are fp32 sums of squares either way.  One workgroup per (image, 32 cells of view 1); its four
+ *          waves take the tiles of 32 cells of view 2; a lane owns a cell of view 1, the score tile lives in the accumulators and is never written.
+ *   limits  b >= 1, 1 <= s <= SSV_DENSE_MATCH_MAX_S (a 16 x 16 map), c % 4 == 0, 4 <= c <= SSV_DENSE_MATCH_MAX_C, b * s < 2^31, eps finite and positive, all
+ *          pointers 16-byte aligned, idx and sim alias neither each other nor an input.  Anything else returns SSV_ERR_INVALID with a message that starts
+ *          "ssv_dense_match:" and touches no output.
+ * ssv_queue_nce: InfoNCE against a queue with one gathered positive per query, loss and gradient in one call.  q [m][d] (normalised by the caller), keys [mk][d],
+ *   pos int32 [m], bank [>= K][d] (rows behind K are never read).  With k+ = keys[pos[i]]:
+ *       s_i+ = (q_i . k+) * inv_temp          s_ij = (q_i . bank_j) * inv_temp,  j < K
+ *       lse[i] = log(exp(s_i+) + sum_j exp(s_ij))                                  [m]
+ *       loss   = mean_i (lse[i] - s_i+)                                            [1]
+ *       dq[i]  = inv_temp / m * (p_i+ k+ + sum_j p_ij bank_j - k+)                 [m][d]
+ *   keys and bank carry no gradient.  All-zero bank rows (a fresh queue) count with score 0, as in the reference's MoCo.  s_ij is the product in the call's
+ *   arithmetic, then one fp32 multiply; s_i+ is a d-long fp32 dot product (the products summed in double and rounded once), then the same multiply.  The maximum
+ *   and lse take the rounded score, the exponents the unrounded product through an fma, the row loss is log(sum) + (max - s_i+); a row's sum, its logarithm, its
+ *   loss and the mean over the rows are carried in double and rounded to fp32 once.
+ *   arithmetic  SSV_ARITH_BF16X3 with d % 32 == 0 and d <= SSV_QUEUE_NCE_FUSED_MAX_D: fused.  Neither the scores nor the probabilities reach memory: ssv_proto_nce's
+ *          pass (bank rows streamed in fp32 and split in registers as the A operand, queries split once per call as the B operand, a lane owns a query, the second
+ *          product accumulated in registers under the online rescale).  A workgroup takes one slice of the queue and one or two tiles of 32 queries; its four
+ *          waves leave (max, sum, acc[d]) of their quarters in the workspace; a second kernel merges them in ascending order, adds the positive as one more
+ *          partial, subtracts its row and writes lse and dq; a third sums the rows' losses in a fixed order.
+ *          SSV_ARITH_F32_MFMA, or another width (these run WHOLLY on fp32 MFMA): per chunk of queries, S through ssv_conv2d_fwd into the workspace (against a
+ *          copy of the queue padded with zero rows to a multiple of 16), a row kernel that reduces S with the positive and overwrites it with d loss / d S,
+ *          and ssv_conv2d_dgrad adding dS bank to the positive's share of dq.  Same contract.  This route takes K <= 2^31 - 16.
+ *   plan   a pure function of (m, K, d, arithmetic); the device is never asked for its size, so the workspace size is the same on every machine and equal
+ *          inputs give equal bits everywhere.  Fused: T = ceil(m / 32) query tiles, KT = 1 for T = 1 or d >= 96, else 2; blocks = ceil(T / KT);
+ *          slices wanted = min(SSV_QUEUE_NCE_MAX_SLICES, ceil(SSV_QUEUE_NCE_TARGET_WGS / blocks), ceil(K / SSV_QUEUE_NCE_SLICE)); a slice has
+ *          L = SSV_QUEUE_NCE_SLICE * ceil(ceil(K / SSV_QUEUE_NCE_SLICE) / wanted) rows and there are ceil(K / L) of them: from 256 blocks on - m > 8160 at
+ *          d >= 96 - the queue is one slice.  Workspace: 4 * slices partials of (d + 2) floats per padded query, the queries' bf16 planes (6 d bytes per padded
+ *          query) and m doubles: 72 MB at 25,088 x 65,536 x 128, where the logits would be 6.1 GiB.  Unfused: chunks of min(1024, 2^25 / Kpad, m) query rows.
+ *   determinism  no floating-point atomics; equal inputs give equal bits whatever the workspace held before.
+ *   bounds  rows of bank behind K and rows of q / pos behind m are never read; of keys only the rows pos names; nothing is written outside loss, lse, dq, flag
+ *          and the workspace.
+ *   bad device data  the call zeroes *flag, then sets bit 0 for a pos[i] outside [0, mk).  The numeric result is then unspecified; every access still stays in
+ *          bounds (the index is clamped where it is an address).  The host reads the flag when it chooses to.
+ *   limits  1 <= m <= SSV_QUEUE_NCE_MAX_M, 1 <= K < 2^31, 1 <= mk < 2^31, d % 4 == 0, 4 <= d <= SSV_KNN_MAX_D, inv_temp finite and positive, all pointers 16-byte
+ *          aligned, the outputs alias neither each other nor an input nor the workspace, ws_bytes >= ssv_queue_nce_workspace_bytes(m, K, d, arithmetic) (0 for
+ *          a refused shape).  Anything else returns SSV_ERR_INVALID with a message that starts "ssv_queue_nce:"; nothing is clamped and no output is touched.
+ * Not built: the data-parallel form, the gradient to keys (DenseCL's key encoder follows by momentum), sampled negatives, maps above 256 cells.
+ * The ABI version stays 124: entry points were only added. */
+#define SSV_DENSE_MATCH_MAX_S 256
+#define SSV_DENSE_MATCH_MAX_C 8192
+#define SSV_QUEUE_NCE_MAX_M 131072
+#define SSV_QUEUE_NCE_FUSED_MAX_D 128
+#define SSV_QUEUE_NCE_SLICE 256
+#define SSV_QUEUE_NCE_MAX_SLICES 32
+#define SSV_QUEUE_NCE_TARGET_WGS 256
+int ssv_dense_match(int32_t b, int32_t s, int32_t c, const float* f1, const float* f2, float eps, int32_t* idx, float* sim, int32_t arithmetic, void* stream);
+size_t ssv_queue_nce_workspace_bytes(int32_t m, int64_t K, int32_t d, int32_t arithmetic);
+int ssv_queue_nce(int32_t m, int32_t d, int64_t K, int64_t mk, const float* q, const float* keys, const int32_t* pos, const float* bank, float inv_temp,
+                  float* loss, float* lse, float* dq, int32_t* flag, int32_t arithmetic, void* ws, size_t ws_bytes, void* stream);
+
 /* ==== "next" row 1 of the scope table: DINO on the reference's ViT (networks/vit.py, models/dino.py) ====================
  * Linear layers of the encoder and of the projection head are ssv_conv2d_fwd/dgrad/wgrad with H = W = R = S = 1 over
  * N = B*T token rows; what follows are the pieces that are not GEMMs.  All matrices are dense row-major fp32. */

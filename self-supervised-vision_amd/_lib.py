@@ -26,6 +26,8 @@ KNN_MAX_K, KNN_MAX_D, KNN_MAX_CLASSES, KNN_MAX_TOPN = 1024, 8192, 4096, 8      #
 NN_LOOKUP_MAX_M, NN_LOOKUP_FUSED_MAX_D, NN_LOOKUP_SLICE, NN_LOOKUP_MAX_SLICES = 8192, 1024, 512, 4096       # SSV_NN_LOOKUP_* (include/ssv_hip.h)
 WHITEN_MAX_D, WHITEN_MAX_W, WMSE_PERM_MAX_N, WMSE_PERM_MAX_VIEWS, WMSE_PERM_MAX_ITERS = 128, 1024, 4096, 8, 16      # SSV_WHITEN_* / SSV_WMSE_PERM_* (include/ssv_hip.h)
 PROTO_NCE_MAX_M, PROTO_NCE_MAX_SEGS, PROTO_NCE_FUSED_MAX_D, PROTO_NCE_SLICE, PROTO_NCE_MAX_SLICES = 8192, 8, 128, 256, 32      # SSV_PROTO_NCE_* (include/ssv_hip.h)
+DENSE_MATCH_MAX_S, DENSE_MATCH_MAX_C = 256, 8192     # SSV_DENSE_MATCH_* (include/ssv_hip.h)
+QUEUE_NCE_MAX_M, QUEUE_NCE_FUSED_MAX_D, QUEUE_NCE_SLICE, QUEUE_NCE_MAX_SLICES, QUEUE_NCE_TARGET_WGS = 131072, 128, 256, 32, 256      # SSV_QUEUE_NCE_* (include/ssv_hip.h)
 VICREG_MAX_D = KNN_MAX_D                             # the VICReg entry points share SSV_KNN_MAX_D (include/ssv_hip.h)
 
 
@@ -190,6 +192,9 @@ SIGNATURES = {
     "ssv_wmse_perm": (C.c_int, [_i32, _i32, _i32, _u64, _u64, _vp, _vp, _vp]),
     "ssv_proto_nce_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32, _i32]),
     "ssv_proto_nce": (C.c_int, [_i32, _i32, _i32, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "ssv_dense_match": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _i32, _vp]),
+    "ssv_queue_nce_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "ssv_queue_nce": (C.c_int, [_i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "ssv_vit_embed_fwd": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ssv_vit_embed_bwd": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "ssv_layernorm_fwd": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),

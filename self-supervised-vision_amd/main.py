@@ -3,9 +3,10 @@
 The flag surface is the reference's (main.py:11-12,38-43), verbatim: -c/--config, -m/--arch, -a/--algo, -t/--task,
 -o/--output, -l/--load with the same choices, so scripts written for the reference keep working.  Algorithms outside the
 accelerated path (deep_cluster, swav, sela) stay on the
-surface and raise NotImplementedError.  Four algorithms are added to the reference's: `-a vicreg` (VICReg, models/vicreg.py; configs/vicreg.yaml),
-`-a nnclr` (NNCLR, models/nnclr.py; configs/nnclr.yaml), `-a wmse` (W-MSE, models/wmse.py; configs/wmse.yaml) and `-a pcl` (Prototypical Contrastive
-Learning, models/pcl.py; configs/pcl.yaml: MoCo plus a ProtoNCE term over k-means prototypes, the one clustering-family trainer here).  Two tasks are added to the reference's three: `-t cluster_eval -l <dir>` loads a checkpoint, runs
+surface and raise NotImplementedError.  Five algorithms are added to the reference's: `-a vicreg` (VICReg, models/vicreg.py; configs/vicreg.yaml),
+`-a nnclr` (NNCLR, models/nnclr.py; configs/nnclr.yaml), `-a wmse` (W-MSE, models/wmse.py; configs/wmse.yaml), `-a pcl` (Prototypical Contrastive
+Learning, models/pcl.py; configs/pcl.yaml: MoCo plus a ProtoNCE term over k-means prototypes, the one clustering-family trainer here) and `-a densecl`
+(DenseCL, models/densecl.py; configs/densecl.yaml: MoCo plus an InfoNCE over every cell of the final feature map, the one dense trainer here).  Two tasks are added to the reference's three: `-t cluster_eval -l <dir>` loads a checkpoint, runs
 k-means on the test-split features with one cluster per class and logs the cluster accuracy after Hungarian matching - the metric of the
 reference's README table, which the reference's own code never computes (optional config block `cluster_eval: {niter, nredo, seed}`);
 `-t knn_eval -l <dir>` loads a checkpoint and logs the top-1 / top-5 accuracy of the weighted kNN classifier (InstDisc / MoCo / DINO's eval_knn:
@@ -26,6 +27,7 @@ NETWORKS = ("resnet18", "resnet50", "resnext50", "resnext101", "wide_resnet50", 
 ALGORITHMS = {"simclr": ("simclr", "SimCLR"), "moco": ("moco", "MoCo"), "byol": ("byol", "BYOL"), "dino": ("dino", "DINO"), "pirl": ("pirl", "PIRL"),
               "barlow": ("barlow", "BarlowTwins"), "simsiam": ("simsiam", "SimSiam"), "relic": ("relic", "ReLIC"), "vicreg": ("vicreg", "VICReg"),
               "nnclr": ("nnclr", "NNCLR"), "wmse": ("wmse", "WMSE"), "pcl": ("pcl", "PCL"),
+              "densecl": ("densecl", "DenseCL"),
               "deep_cluster": None, "swav": None, "sela": None}
 
 _FLAGS = (

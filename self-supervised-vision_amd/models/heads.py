@@ -6,6 +6,7 @@ Parameter names, shapes and init draws follow the reference so state_dicts and s
   VICReg ProjectionHead  (not in the reference)   Barlow's three layers without the final L2 normalisation
   NNCLR  Projection/PredictionHead  (not in the reference)   layer1.{0,1} layer2.{0,1} layer3.{0,1}  /  layer1.{0,1} layer2
   W-MSE  ProjectionHead  (not in the reference)   layer1.{0,1} layer2, not normalised
+  DenseCL DenseProjectionHead  (not in the reference)   layer1.{0,1} layer2 on the rows of the feature map
 """
 import math
 
@@ -143,6 +144,20 @@ class WmseProjectionHead(hnn.HipModule):
     def _run(self, tape, x):
         h = self.layer1._run(tape, x)
         return _narrow_linear(tape, h, self.layer2) if self.narrow else self.layer2._run(tape, h)
+
+
+class DenseProjectionHead(hnn.HipModule):
+    """DenseCL's dense projector on the rows [B * cells, C] of the final feature map (the paper's 1x1 conv - ReLU - 1x1 conv, which on rows is two Linear
+    layers): layer1 = Linear(C, C)-BN-ReLU, layer2 = Linear(C, D).  The paper's head has no BatchNorm; the heads of this project are built on the fused BN + ReLU
+    kernel and there is no stand-alone ReLU, so layer1 carries one (its statistics run over all cells of the batch).  The loss normalises the output."""
+
+    def __init__(self, input_dim, output_dim):
+        super().__init__()
+        self.layer1 = _LinearBnRelu(input_dim, input_dim)
+        self.layer2 = _fresh_linear(input_dim, output_dim)
+
+    def _run(self, tape, x):
+        return self.layer2._run(tape, self.layer1._run(tape, x))
 
 
 class VicregProjectionHead(BarlowProjectionHead):

@@ -56,12 +56,13 @@ class MoCo(TwoViewTrainer):
     algo = "moco"
     graph_safe = True    # the queue pointer is device memory (MemoryBank); momentum update and queue push are part of the step and of its graph
     graph_inputs = ("aug_1", "aug_2")
+    encoder_model = EncoderModel     # the bridged module of both encoders (DenseCL's also yields the dense grid)
 
     def _build(self, arch):
         encoder, encoder_dim = NETWORKS[arch].values()
         cfg = self.config
-        self.query_encoder = EncoderModel(encoder(**cfg["encoder"]), encoder_dim, cfg["proj_dim"]).to(self.device)
-        self.key_encoder = EncoderModel(encoder(**cfg["encoder"]), encoder_dim, cfg["proj_dim"]).to(self.device)   # its init draws are consumed, then overwritten
+        self.query_encoder = self.encoder_model(encoder(**cfg["encoder"]), encoder_dim, cfg["proj_dim"]).to(self.device)
+        self.key_encoder = self.encoder_model(encoder(**cfg["encoder"]), encoder_dim, cfg["proj_dim"]).to(self.device)   # its init draws are consumed, then overwritten
         self.memory_bank = MemoryBank(cfg["queue_size"], cfg["proj_dim"], self.device)
         self.m = cfg.get("momentum", 0.999)
         self.key_encoder.load_state_dict(self.query_encoder.state_dict())

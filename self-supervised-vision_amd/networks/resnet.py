@@ -150,14 +150,18 @@ class ResNet(hnn.HipModule):
         return [list(self.conv1.parameters()) + list(self.bn1.parameters())] + \
                [list(getattr(self, f"layer{idx}").parameters()) for idx in range(1, len(_STAGE_PLANES) + 1)]
 
-    def _run(self, tape, x):
+    def _feature_map(self, tape, x):
+        """The stem and the four stages: the final feature map [B, H', W', out_dim] (it may still be a LazySum: its first consumer forms it)"""
         hnn.stage_mark(tape, self, 0)
         x = hnn.bn_relu_maxpool(tape, self.conv1._run(tape, x, bn_stats=True), self.bn1)      # one pass each way when the conv left statistics
         for idx in range(1, len(_STAGE_PLANES) + 1):
             hnn.stage_mark(tape, self, idx)      # fires in backward once this stage's weight gradients are enqueued
             for unit in getattr(self, f"layer{idx}"):
                 x = unit._run(tape, x)
-        return hnn.global_avgpool(tape, x)
+        return x
+
+    def _run(self, tape, x):
+        return hnn.global_avgpool(tape, self._feature_map(tape, x))
 
 
 # name -> (unit, units per stage, fixed constructor keywords)

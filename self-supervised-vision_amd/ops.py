@@ -1146,6 +1146,67 @@ def check_proto_nce_flag(flag):
         raise _lib.SsvError("proto_nce: an inverse concentration is not finite and positive")
 
 
+# ------------------------------------------------------------------------------------------- DenseCL's pieces: the dense matching and the queue InfoNCE (csrc/densecl.hip)
+def dense_match(f1, f2, eps=1e-12):
+    """(idx int32 [b, s], sim [b, s]) of two backbone feature maps f1, f2 [b, ..., c] (NHWC maps, or [b, s, c] rows): for every cell of f1 the cell of f2 of the same
+    image with the largest f1 . f2 / max(|f2|, eps), lowest cell among equal scores, as the row n * s + j of the [b * s, d] key grid, and the cosine of the pair
+    (include/ssv_hip.h: ssv_dense_match).  At most 256 cells per image, c % 4 == 0.  Only enqueues: no host synchronisation, capturable in a step graph."""
+    _lib._dev(f1, f2)
+    if f1.dim() < 3 or f1.shape != f2.shape or f1.dtype != torch.float32 or f2.dtype != torch.float32 or not (f1.is_contiguous() and f2.is_contiguous()):
+        raise _lib.SsvError(f"dense_match: two contiguous fp32 maps of one shape [b, ..., c] expected (got {tuple(f1.shape)} {f1.dtype}, {tuple(f2.shape)} {f2.dtype})")
+    b, c = f1.shape[0], f1.shape[-1]
+    s = f1.numel() // max(b * c, 1)
+    if b < 1 or not 1 <= s <= _lib.DENSE_MATCH_MAX_S or c < 4 or c % 4 or c > _lib.DENSE_MATCH_MAX_C:
+        raise _lib.SsvError(f"dense_match: need 1 <= cells <= {_lib.DENSE_MATCH_MAX_S}, c % 4 == 0 and 4 <= c <= {_lib.DENSE_MATCH_MAX_C} (got b = {b}, cells = {s}, c = {c})")
+    idx = torch.empty((b, s), dtype=torch.int32, device=f1.device)
+    sim = _empty((b, s), f1)
+    call("ssv_dense_match", b, s, c, ptr(f1), ptr(f2), float(eps), ptr(idx), ptr(sim), _arith_code(), stream())
+    return idx, sim
+
+
+def queue_nce_route(d):
+    """"fused" or "unfused": the route ssv_queue_nce takes at width d under the current arithmetic (include/ssv_hip.h: ssv_queue_nce, `arithmetic`)"""
+    return "fused" if ARITHMETIC == "bf16x3" and d % 32 == 0 and d <= _lib.QUEUE_NCE_FUSED_MAX_D else "unfused"
+
+
+def queue_nce(q, keys, pos, bank, K, inv_temp):
+    """(loss 0-d, lse [m], dq [m, d], flag int32 [1]) of InfoNCE against a queue with one gathered positive per query: q [m, d] (normalised by the caller), the
+    positive of query i is keys[pos[i]] (keys [mk, d], pos int32 [m]), the negatives are the first ``K`` rows of bank [>= K, d], every score times ``inv_temp``
+    (include/ssv_hip.h: ssv_queue_nce).  flag bit 0: a pos outside [0, mk) - left on the device for the caller to read when it chooses.  Contiguous device
+    tensors, d % 4 == 0, m <= 131072.  Only enqueues: no host synchronisation, capturable in a step graph."""
+    _lib._dev(q, keys, pos, bank)
+    if (q.dim() != 2 or keys.dim() != 2 or bank.dim() != 2 or pos.dim() != 1 or q.dtype != torch.float32 or keys.dtype != torch.float32
+            or bank.dtype != torch.float32 or pos.dtype != torch.int32):
+        raise _lib.SsvError(f"queue_nce: fp32 q [m, d], keys [mk, d], bank [>= K, d] and int32 pos [m] expected (got {tuple(q.shape)} {q.dtype}, {tuple(keys.shape)} "
+                            f"{keys.dtype}, {tuple(bank.shape)} {bank.dtype}, {tuple(pos.shape)} {pos.dtype})")
+    if not (q.is_contiguous() and keys.is_contiguous() and pos.is_contiguous() and bank.is_contiguous()):
+        raise _lib.SsvError("queue_nce: q, keys, pos and bank must be contiguous")
+    (m, d), (mk, dk), (rows, db), K = q.shape, keys.shape, bank.shape, int(K)
+    if dk != d or db != d or d < 4 or d % 4 or d > _lib.KNN_MAX_D or not 1 <= m <= _lib.QUEUE_NCE_MAX_M or mk < 1 or pos.shape[0] != m:
+        raise _lib.SsvError(f"queue_nce: q, keys and bank must share d columns, d % 4 == 0, 4 <= d <= {_lib.KNN_MAX_D}, 1 <= m <= {_lib.QUEUE_NCE_MAX_M}, pos [m] "
+                            f"(got q {tuple(q.shape)}, keys {tuple(keys.shape)}, bank {tuple(bank.shape)}, pos {tuple(pos.shape)})")
+    if not 1 <= K <= rows:
+        raise _lib.SsvError(f"queue_nce: K must lie in [1, {rows} rows of the bank] (got {K})")
+    if not (float(inv_temp) > 0.0 and float(inv_temp) < float("inf")):
+        raise _lib.SsvError(f"queue_nce: inv_temp must be finite and positive (got {inv_temp})")
+    arith = _arith_code()
+    ws = workspace.get(max(_lib.load().ssv_queue_nce_workspace_bytes(m, K, d, arith), 16), q.device)
+    loss = torch.empty((1,), dtype=torch.float32, device=q.device)
+    lse = torch.empty((m,), dtype=torch.float32, device=q.device)
+    dq = torch.empty((m, d), dtype=torch.float32, device=q.device)
+    flag = torch.empty(1, dtype=torch.int32, device=q.device)
+    call("ssv_queue_nce", m, d, K, mk, ptr(q), ptr(keys), ptr(pos), ptr(bank), float(inv_temp), ptr(loss), ptr(lse), ptr(dq), ptr(flag), arith, ptr(ws), ws.numel(),
+         stream())
+    return loss.view(()), lse, dq, flag
+
+
+def check_queue_nce_flag(flag):
+    """Reads the flag of a queue_nce call (one host synchronisation) and raises SsvError for what it reports."""
+    bits = 0 if flag is None else int(flag.item())
+    if bits & 1:
+        raise _lib.SsvError("queue_nce: a positive's index lies outside the key grid")
+
+
 # ------------------------------------------------------------------------------------------- ViT / DINO pieces
 LN_EPS = 1e-5
 ATTENTION_BF16X3 = True      # the attention forward's two products in the bf16x3 arithmetic when ops.ARITHMETIC says so (the backward stays on the fp32 instruction)

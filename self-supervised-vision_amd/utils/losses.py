@@ -536,6 +536,47 @@ class ProtoNceLoss(nn.Module):
         return _ProtoNceFn.apply(query, protos, inv_phi, labels, tuple(int(e) for e in seg_end), self)
 
 
+class _DenseNceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query, keys, pos, bank, queue_size, module):
+        # keys and the queue carry no gradient: one call gives the loss and d loss / dq (csrc/densecl.hip); backward only scales, as in _MocoFn
+        d = query.shape[1]
+        qn, inv_q = ops.l2norm_fwd(query.detach().contiguous(), module.normalize)
+        kn, _ = ops.l2norm_fwd(keys.detach().contiguous(), module.normalize)
+        loss, module.last_lse, dq, module.last_flag = ops.queue_nce(qn, kn, pos, bank, queue_size, 1.0 / float(module.temperature))
+        ctx.saved = ops.l2norm_bwd(qn, inv_q, dq, d, module.normalize)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        return ops.scale_(ctx.saved, dloss.contiguous()), None, None, None, None, None
+
+
+class DenseNceLoss(nn.Module):
+    """The dense term of DenseCL (Wang et al., CVPR 2021; not in the reference): InfoNCE of every cell's embedding ``query`` [M, D] against the dense queue
+    ``memory_vectors`` [>= queue_size, D], the positive of cell i being row ``pos[i]`` (int32, from ops.dense_match) of ``keys`` [Mk, D].  Both grids are
+    L2-normalised here (``normalize``); gradients reach ``query`` only.  D % 4 == 0 (a multiple of 32 up to 128 takes the fused kernel), M <= 131072.
+    ``last_flag`` (device int32 [1]; ops.check_queue_nce_flag) and ``last_lse`` belong to the last forward: the flag is NOT read here - a trainer reads it once
+    per epoch."""
+
+    def __init__(self, normalize=True, temperature=1.0):
+        super().__init__()
+        self.normalize, self.temperature = bool(normalize), float(temperature)
+        self.last_flag = self.last_lse = None
+
+    def forward(self, query, keys, pos, memory_vectors, queue_size=None):
+        if (query.dim() != 2 or keys.dim() != 2 or memory_vectors.dim() != 2 or keys.shape[1] != query.shape[1] or memory_vectors.shape[1] != query.shape[1]
+                or query.shape[1] % 4 or not 1 <= query.shape[0] <= _lib.QUEUE_NCE_MAX_M or pos.dim() != 1 or pos.shape[0] != query.shape[0]):
+            raise ValueError(f"DenseNceLoss needs query [M, D], keys [Mk, D], a queue [K, D] and pos [M] with D % 4 == 0 and M <= {_lib.QUEUE_NCE_MAX_M}, got "
+                             f"{tuple(query.shape)}, {tuple(keys.shape)}, {tuple(memory_vectors.shape)} and {tuple(pos.shape)}")
+        if not self.temperature > 0.0:
+            raise ValueError(f"DenseNceLoss needs a positive temperature (got {self.temperature})")
+        if hdist.is_on():
+            raise NotImplementedError("DenseNceLoss is single-process: the dense queue is not replicated across ranks")
+        k = memory_vectors.shape[0] if queue_size is None else int(queue_size)
+        return _DenseNceFn.apply(query, keys, pos, memory_vectors, k, self)
+
+
 class _PirlFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img_features, patch_features, bank, pos_index, neg_index, module):

@@ -27,6 +27,7 @@ CLASSES = (
     ("misc", "nn_prep_k"), ("misc", "nn_fused_k"), ("misc", "nn_rowarg_k"), ("misc", "nn_fold_k"),
     ("loss", "whiten_fwd_k"), ("loss", "whiten_bwd_k"), ("misc", "wmse_perm_k"), ("misc", "wmse_step_advance_k"),
     ("loss", "pn_check_k"), ("loss", "pn_loss_k"), ("loss", "pn_prep_k"), ("loss", "pn_fused_k"), ("loss", "pn_fold_k"), ("loss", "pn_pad_k"), ("loss", "pn_row_k"),
+    ("loss", "dm_match_k"), ("loss", "qn_loss_k"), ("loss", "qn_prep_k"), ("loss", "qn_fused_k"), ("loss", "qn_fold_k"), ("loss", "qn_pad_k"), ("loss", "qn_row_k"),
 )
 CONV_FAMILY = ("conv_fwd", "conv_dgrad", "conv_wgrad")
 # host functions whose kernels run under another class's scope than the table gives them - both inside the conv family, so the family sums agree:
