@@ -1,4 +1,5 @@
-"""The oracle of the DenseCL tests (tests/test_densecl_cpu.py, tests/test_gpu_dense_nce.py, tests/test_gpu_densecl.py): the dense matching, the queue InfoNCE and the
+"""The oracle of the DenseCL tests (tests/test_densecl_cpu.py, tests/test_gpu_dense_nce.py, tests/test_gpu_densecl.py and the launch-form files
+tests/test_gpu_dense_nce_forms.py, tests/test_gpu_dense_match_forms.py): the dense matching, the queue InfoNCE and the
 trainer's combined loss in plain torch under autograd (float64, or the same lines in float32), the case tables the kernel tests run and a restatement of the
 kernel's launch plan.  Nothing here touches the GPU or the library.
 
@@ -13,6 +14,7 @@ FACTOR = 8.0                         # measured there on an MI355X (profiles/den
 SLICE, MAX_SLICES, TARGET_WGS = 256, 32, 256          # SSV_QUEUE_NCE_SLICE, _MAX_SLICES, _TARGET_WGS
 CHUNK_ROWS, CHUNK_ELEMS = 1024, 1 << 25               # the unfused route's query chunk (csrc/densecl.hip)
 MAX_M, MATCH_MAX_S = 131072, 256                      # SSV_QUEUE_NCE_MAX_M, SSV_DENSE_MATCH_MAX_S
+MATCH_MAX_C = 8192                                    # SSV_DENSE_MATCH_MAX_C
 TIE = 8 * 2.0 ** -24                 # a chosen cell whose fp64 cosine is this close to the best one is excused (at most 1 % of a case's cells)
 
 
@@ -137,22 +139,22 @@ def _unit(x):
 
 
 def make_case(case, seed=0):
-    """(q [m, d], keys [mk, d], pos int32 [m], bank [K, d], K, inv_temp): fp32 unit rows (|q . k| <= 1) and inv_temp = 5 (a temperature of 0.2), so |s| <= 5;
-    mk = m + 3; pos at the first key, at the last, otherwise drawn.  The positive leans on its query (cosine about 0.3), as a matched cell does."""
+    """(q [m, d], keys [mk, d], pos int32 [m], bank [K, d], K, inv_temp): fp32 unit rows (|q . k| <= 1) and inv_temp = 5 (a temperature of 0.2), so |s| <= 5
+    (the variant `climb`: CLIMB_INV_TEMP); mk = m + 3; pos at the first key, at the last, otherwise drawn.  The positive leans on its query (cosine about 0.3),
+    as a matched cell does."""
     m, d, K, variant = case
     g = torch.Generator().manual_seed(1000 * seed + 7 * m + 13 * d + K)
     mk = m + 3
     q = _unit(torch.randn(m, d, generator=g, dtype=torch.float64))
     keys = _unit(torch.randn(mk, d, generator=g, dtype=torch.float64))
     bank = _unit(torch.randn(K, d, generator=g, dtype=torch.float64))
-    drawn = torch.randint(0, mk, (m,), generator=g)
-    pos = torch.tensor([(0, mk - 1, int(drawn[i]))[i % 3] for i in range(m)], dtype=torch.int32)
+    drawn = torch.randint(0, mk, (m,), generator=g).tolist()
+    pos = torch.tensor([(0, mk - 1, drawn[i])[i % 3] for i in range(m)], dtype=torch.int32)
     if variant == "same":                              # every query has the same positive
         pos[:] = mk // 2
     else:
-        for i in range(m):
-            if i % 3 == 2:
-                keys[int(pos[i])] = _unit((keys[int(pos[i])] + 0.3 * q[i])[None])[0]
+        for i in range(2, m, 3):
+            keys[drawn[i]] = _unit((keys[drawn[i]] + 0.3 * q[i])[None])[0]
     if variant == "dup":                               # rows 255 | 256 lie in two slices (and two workgroups): the same row twice
         bank[256] = bank[255]
     if variant == "late":                              # every query leans towards one direction, which is the LAST bank row: the running maximum is replaced in the last tile
@@ -161,7 +163,36 @@ def make_case(case, seed=0):
         bank[K - 1] = lean[0]
     if variant == "zero":                              # the fresh queue
         bank.zero_()
-    return q.float(), keys.float(), pos, bank.float(), K, 5.0
+    if variant == "dupL":                              # as dup, at the boundary of the bf16x3 plan's LONG slices (FORM_CASES: rows FORM_DUP_ROW - 1 | FORM_DUP_ROW)
+        bank[FORM_DUP_ROW] = bank[FORM_DUP_ROW - 1]
+    if variant == "climb":                             # the queries lean on one direction and the bank rows are sorted ascending by their product with it: the
+        lean = _unit(torch.randn(1, d, generator=g, dtype=torch.float64))      # running maximum is replaced tile after tile, at a temperature of 0.07
+        q = _unit(q + 1.5 * lean)
+        bank = bank[torch.argsort(bank @ lean[0])]
+    return q.float(), keys.float(), pos, bank.float(), K, (CLIMB_INV_TEMP if variant == "climb" else 5.0)
+
+
+# ---- the launch forms (tests/test_gpu_dense_nce_forms.py) ----------------------------------------------------------------------------------------------------
+LONG = 8200                                           # past SLICE * MAX_SLICES rows: slices of 2 * SLICE rows, 17 of them, the last of 8 rows
+FORM_DUP_ROW = 2 * SLICE                              # the first row of the second slice of that plan
+CLIMB_INV_TEMP = 1.0 / 0.07
+CLAMP = 32800                                         # a multiple of 16 above 2^25 / 1024: the chunk of the unfused route is 2^25 // 32800 = 1023 rows
+FORM_CASES = [(33, 32, LONG, "plain"), (33, 128, LONG, "late"), (1, 64, LONG, "plain"), (97, 64, LONG, "dupL"), (33, 36, LONG, "plain"),
+              (70, 64, 255, "plain"), (70, 64, 256, "plain"), (70, 64, 257, "plain"),
+              (70, 96, 65, "plain"), (70, 32, 129, "plain"), (70, 128, 193, "plain"),
+              (1030, 4, CLAMP, "plain"), (1030, 36, CLAMP, "plain"),
+              (70, 96, 640, "climb"), (70, 64, LONG, "climb"), (33, 128, LONG, "climb"), (70, 36, 640, "climb"),
+              (MAX_M, 32, 33, "plain")]
+FORM_ROUTES_AGREE = [(33, 128, LONG, "late"), (70, 64, LONG, "climb")]
+
+
+def climbing_tiles(q, bank):
+    """(the mean over the queries of the number of 32-row tiles whose largest score is above that of every tile before them, the number of tiles)"""
+    sc = q.double() @ bank.double().T
+    tiles = -(-sc.shape[1] // 32)
+    top = torch.stack([sc[:, 32 * t:32 * t + 32].max(dim=1).values for t in range(tiles)], dim=1)
+    raised = top[:, 1:] > torch.cummax(top, dim=1).values[:, :-1]
+    return float(raised.sum(dim=1).double().mean()), tiles
 
 
 MATCH_CASES = [(3, 1, 8, "plain"), (5, 16, 64, "plain"), (4, 49, 512, "plain"), (3, 50, 36, "plain"), (2, 256, 128, "plain"), (1, 256, 2048, "plain"),
@@ -174,32 +205,85 @@ def match_id(case):
     return f"b{b}-s{s}-c{c}-{variant}"
 
 
+# the launch forms of dm_match_k (tests/test_gpu_dense_match_forms.py): (b, s, c, variant)
+FORM_MATCH_CASES = [(2, 32, 64, "plain"), (3, 33, 64, "plain"), (2, 64, 36, "plain"), (7, 65, 64, "plain"), (2, 96, 64, "plain"), (2, 97, 64, "plain"),
+                    (2, 128, 128, "plain"), (2, 129, 128, "plain"), (1, 160, 64, "plain"), (1, 255, 64, "plain"),
+                    (2, 256, 64, "perm"), (2, 129, 128, "perm"), (2, 33, 36, "perm"),
+                    (2, 256, 64, "ties"),
+                    (2, 50, 64, "eps"), (1, 256, 128, "eps"),
+                    (2, 50, 64, "nan"),
+                    (3, 16, 4, "signed"), (3, 16, 12, "signed"), (2, 50, 24, "signed"), (2, 129, 8, "signed"), (1, 33, MATCH_MAX_C, "plain")]
+MATCH_EPS = 0.5                                       # the eps of the variant `eps`; every other case calls with 1e-12
+TIES = {37: 5, 133: 5, 165: 5, 130: 100}              # variant `ties`, image 0: cell of f2 -> the cell it is a copy of
+TIES_F1 = {0: 5, 40: 5, 1: 100, 255: 100}             # ... and cell of f1 -> the cell of f2 it is a copy of
+NAN_CELL = (1, 7, 3)                                  # variant `nan`: (image, cell, channel) of f1
+
+
+def match_eps(case):
+    return MATCH_EPS if case[3] == "eps" else 1e-12
+
+
 def make_match_case(case, seed=0):
     """(f1, f2) [b, s, c] fp32: ReLU of standard normal features, as a backbone's are.  planted: in image 0 cell 7 of f2 is a copy of cell 3 (an exact tie, which
-    must resolve to 3) and cell 0 of f1 is that cell too; in the last image row 1 of f1 is zero (it picks j = 0) and row 2 of f2 is zero (it is never chosen over a positive score)."""
+    must resolve to 3) and cell 0 of f1 is that cell too; in the last image row 1 of f1 is zero (it picks j = 0) and row 2 of f2 is zero (it is never chosen over a positive score).
+    The variants of FORM_MATCH_CASES -
+    signed: no ReLU (at c = 4 the ReLU leaves all-zero rows, which tie at 0);
+    perm:   f1[n] = f2[n][p[n]] for drawn permutations p (match_perm): by Cauchy-Schwarz the arg-max of cell i is p[n][i] and its cosine 1;
+    ties:   in image 0 the cells TIES of f2 are copies of lower cells and the cells TIES_F1 of f1 are copies of those originals;
+    eps:    every second cell of f2 is scaled by 0.01 and the call takes eps = MATCH_EPS, which is returned as a third element: (f1, f2, eps);
+    nan:    one channel of one cell of f1 (NAN_CELL) is NaN."""
     b, s, c, variant = case
     g = torch.Generator().manual_seed(1000 * seed + 7 * b + 13 * s + c)
-    f1 = torch.relu(torch.randn(b, s, c, generator=g))
-    f2 = torch.relu(torch.randn(b, s, c, generator=g))
+    f1 = torch.randn(b, s, c, generator=g)
+    f2 = torch.randn(b, s, c, generator=g)
+    if variant != "signed":
+        f1, f2 = torch.relu(f1), torch.relu(f2)
     if variant == "planted":
         f2[0, 7] = f2[0, 3]
         f1[0, 0] = f2[0, 3]                            # cell 0 of image 0 certainly matches the duplicated cell
         f1[b - 1, 1] = 0.0
         f2[b - 1, 2] = 0.0
+    if variant == "perm":
+        p = torch.stack([torch.randperm(s, generator=g) for _ in range(b)])
+        f1 = torch.gather(f2, 1, p[:, :, None].expand(b, s, c))
+    if variant == "ties":
+        for copy, orig in TIES.items():
+            f2[0, copy] = f2[0, orig]
+        for cell, orig in TIES_F1.items():
+            f1[0, cell] = f2[0, orig]
+    if variant == "nan":
+        f1[NAN_CELL] = float("nan")
+    if variant == "eps":
+        f2[:, ::2] *= 0.01
+        return f1.contiguous(), f2.contiguous(), MATCH_EPS
     return f1.contiguous(), f2.contiguous()
 
 
+def match_perm(case, seed=0):
+    """the permutations [b, s] the variant `perm` drew: make_match_case's generator after its two draws"""
+    b, s, c, variant = case
+    g = torch.Generator().manual_seed(1000 * seed + 7 * b + 13 * s + c)
+    torch.randn(b, s, c, generator=g), torch.randn(b, s, c, generator=g)
+    return torch.stack([torch.randperm(s, generator=g) for _ in range(b)])
+
+
 def match_gap(case, ref):
-    """The smallest fp64 gap between the best and the second-best cosine over the cells that have one: a planted copy counts as its original and an all-zero
-    f1 row has no best"""
+    """The smallest fp64 gap between the best and the second-best cosine over the cells that have one: a planted copy counts as its original, an all-zero
+    f1 row has no best and neither has a cell of f1 that holds a NaN"""
     b, s, c, variant = case
     cos = ref["cos"].clone()
     if s < 2:
         return float("inf")
     if variant == "planted":
         cos[0, :, 7] = -1.0
+    if variant == "ties":
+        cos[0, :, list(TIES)] = -1.0
+    if variant == "nan":
+        cos[NAN_CELL[0], NAN_CELL[1]] = 0.0
     top = cos.topk(2, dim=2).values
     gap = top[:, :, 0] - top[:, :, 1]
     if variant == "planted":
         gap[b - 1, 1] = float("inf")
+    if variant == "nan":
+        gap[NAN_CELL[0], NAN_CELL[1]] = float("inf")
     return float(gap.min())

@@ -283,7 +283,7 @@ def test_plan_restatement_is_the_librarys():
 
 def test_cases_reach_every_launch_form():
     """All six (DT, KT) instantiations the dispatch of ssv_queue_nce can launch; the sliced and the unsliced plan (three, two and one slice at K = 640, each
-    reached by an m just past its threshold); a slice of more than SSV_QUEUE_NCE_SLICE rows is left to the plan test (it needs K > 8192); more than one chunk
+    reached by an m just past its threshold); many slices of more than SSV_QUEUE_NCE_SLICE rows need K > 8192 and run in tests/test_gpu_dense_nce_forms.py (FORM_CASES, below); more than one chunk
     of the unfused route in both arithmetics; the unfused route under bf16x3 at a width that is a multiple of 32; both tile counts of the matching kernel"""
     plans = {c: do.plan(c[0], c[2], c[1], "bf16x3") for c in do.cases()}
     assert {(p["DT"], p["KT"]) for p in plans.values() if p["fused"]} == {(1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (4, 1)}
@@ -309,3 +309,161 @@ def test_the_accuracy_bound_is_what_the_committed_report_implies():
     want = {f"{do.case_id(c)}[{a}].{k}" for c in do.cases() for a in ARITHS for k in ("loss", "lse", "dq")}
     want |= {f"match-{do.match_id(c)}[{a}].sim" for c in do.MATCH_CASES for a in ARITHS}
     assert set(doc["cases"]) == want and re.fullmatch(r"[0-9a-f]{16}", doc["source_sha16"])
+
+
+# ---- the launch forms of tests/test_gpu_dense_nce_forms.py and tests/test_gpu_dense_match_forms.py ----------------------------------------------------------------
+def test_form_cases_reach_every_launch_form():
+    """Every case of densecl_oracle.FORM_CASES reaches, by the restated plan (held against the library's workspace size here too), the form its label names in
+    each arithmetic; between them the labels see what the older table leaves out: a slice of 2 * SLICE rows in four instantiations with a last slice of 8 rows,
+    K on either side of one slice and one row into every quarter, the clamped chunk of the unfused route in both arithmetics, the largest m; and the label
+    table of the GPU file is the one its cases name."""
+    import test_gpu_dense_nce_forms as forms
+    from ssv_amd import _lib
+    lib = _lib.load()
+    cases = do.FORM_CASES
+    assert len(set(cases)) == len(cases) == 18 and not set(cases) & set(do.cases()) and set(do.FORM_ROUTES_AGREE) <= set(cases) and len(do.FORM_ROUTES_AGREE) == 2
+    assert {c[3] for c in do.FORM_ROUTES_AGREE} == {"late", "climb"} and all(c[2] == do.LONG for c in do.FORM_ROUTES_AGREE)
+    assert set(forms.CASE_LABELS) == set(cases) and forms.ARITHS == ARITHS
+    for case, labels in forms.CASE_LABELS.items():
+        m, d, K, _ = case
+        for arith, label in zip(ARITHS, labels):
+            assert not label or forms.reaches(label, case, arith), (case, arith, label)
+            assert not forms.reaches("quarter.edge" if label != "quarter.edge" else "m.max", case, arith)       # reaches() tells the forms apart
+            code = _lib.ARITH_BF16X3 if arith == "bf16x3" else _lib.ARITH_F32_MFMA
+            assert lib.ssv_queue_nce_workspace_bytes(m, K, d, code) == do.plan(m, K, d, arith)["bytes"] <= 160 << 20, (case, arith)
+    by = lambda label, a: [c for c, l in forms.CASE_LABELS.items() if l[a] == label]
+    plans = lambda label, arith: [do.plan(c[0], c[2], c[1], arith) for c in by(label, ARITHS.index(arith))]
+    # slice.long: L = 512, 17 slices, the last of 8 rows (three empty quarters, quarter 0 clipped at K); four instantiations; unfused at d = 36 and under f32
+    long_ = plans("slice.long", "bf16x3")
+    assert {(p["DT"], p["KT"]) for p in long_ if p["fused"]} == {(1, 2), (4, 1), (2, 1), (2, 2)} and sum(not p["fused"] for p in long_) == 1
+    assert all((p["rows"], p["slices"]) == (2 * do.SLICE, 17) and do.LONG - 16 * p["rows"] == 8 for p in long_ if p["fused"])
+    assert all(p["kp"] == 8208 for p in plans("slice.long", "f32")) and all(p.get("rows", 0) <= do.SLICE or p["slices"] <= 2 for p in (do.plan(c[0], c[2], c[1], "bf16x3") for c in do.cases()))      # the older table: one or two long slices at most
+    assert {c[3] for c in by("slice.long", 0)} == {"plain", "late", "dupL"} and do.FORM_DUP_ROW == 2 * do.SLICE
+    assert {c[2] for c in by("slice.edge", 0)} == {do.SLICE - 1, do.SLICE, do.SLICE + 1} and {p["kp"] for p in plans("slice.edge", "f32")} == {256, 272}
+    assert {c[2] for c in by("quarter.edge", 0)} == {65, 129, 193} and {p["DT"] for p in plans("quarter.edge", "bf16x3")} == {1, 3, 4}
+    for arith in ARITHS:
+        clamp = plans("chunk.clamp", arith)
+        assert len(clamp) == 2 and all((p["cr"], p["chunks"], p["kp"]) == (1023, 2, 32800) for p in clamp) and {c[1] for c in by("chunk.clamp", 0)} == {4, 36}
+        assert all(do.plan(c[0], c[2], c[1], arith).get("cr", 0) != 1023 for c in do.cases())
+    assert {(c[1], c[2]) for c in by("temp.climb", 0)} == {(96, 640), (64, do.LONG), (128, do.LONG), (36, 640)}
+    assert [(p["T"], p["blocks"]) for p in plans("m.max", "bf16x3")] == [(4096, 2048)] and [p["chunks"] for p in plans("m.max", "f32")] == [128]
+    assert max(c[0] for c in do.cases()) < do.MAX_M == by("m.max", 0)[0][0]
+    doc = forms.documented_labels()
+    assert len(doc) == 9 and set(doc.values()) == {"ssv_queue_nce"}
+    used = {b for labels in forms.TARGETS.values() for b in labels.split()}
+    assert not set(doc) - used, f"documented branches without a case: {sorted(set(doc) - used)}"
+    assert not used - set(doc), f"cases name undocumented branches: {sorted(used - set(doc))}"
+    assert set(forms.TARGETS) == {name for name in dir(forms) if name.startswith("test_")}
+
+
+@pytest.mark.parametrize("case", do.FORM_CASES, ids=do.case_id)
+def test_form_cases_keep_the_fp32_reference_meaningful(case):
+    """In fp64: the mean probability of the positive is below 0.9, no score leaves [-60, 60] and dq is not zero; the planted variants are what they say"""
+    q, keys, pos, bank, K, it = do.make_case(case)
+    m, d, k, variant = case
+    assert q.shape == (m, d) and keys.shape == (m + 3, d) and pos.shape == (m,) and pos.dtype == torch.int32 and bank.shape == (k, d) and K == k
+    assert 0 <= int(pos.min()) and int(pos.max()) < m + 3 and it == (do.CLIMB_INV_TEMP if variant == "climb" else 5.0)
+    ref, r32 = do.queue_nce(q, keys, pos, bank, K, it), do.queue_nce(q, keys, pos, bank, K, it, dtype=torch.float32)
+    print(f"{do.case_id(case)}: pos {ref['pos']:.3g} smax {ref['smax']:.3g} e(ref32) of dq {do.errs(r32['dq'], ref['dq'])[0]:.3g}")
+    assert ref["pos"] < 0.9, ref["pos"]
+    assert ref["smax"] <= 60.0, ref["smax"]
+    assert float(ref["dq"].abs().max()) > 0.0 and float(ref["loss"]) > 0.0
+    if variant == "late":
+        assert bool(((q.double() @ bank.double().T).argmax(dim=1) == K - 1).all())
+    if variant == "dupL":
+        r = do.FORM_DUP_ROW
+        assert torch.equal(bank[r], bank[r - 1]) and do.plan(m, k, d, "bf16x3")["rows"] == r and not torch.equal(bank[r], bank[r + 1])
+    if variant == "climb":
+        assert abs(it - 1.0 / 0.07) < 1e-12
+        raised, tiles = do.climbing_tiles(q, bank)
+        print(f"{do.case_id(case)}: {raised:.1f} of {tiles} tiles raise the running maximum")
+        if k == 640:
+            assert tiles == 20 and raised >= 0.25 * tiles, raised
+        assert raised >= 5.0, raised
+
+
+def test_match_form_cases_reach_their_labels():
+    """Every case of densecl_oracle.FORM_MATCH_CASES is the form its label names, and the labels between them hold every edge of dm_match_k's tiling: s on both
+    sides of each tile of NT = 1, the NT switch, an empty second tile, the clamp inside the last tile, every accumulator position, the slab tails and both
+    channel limits"""
+    import test_gpu_dense_match_forms as forms
+    cases = do.FORM_MATCH_CASES
+    assert len(set(cases)) == len(cases) == 22 and not set(cases) & set(do.MATCH_CASES) and set(forms.CASE_LABELS) == set(cases) and forms.ARITHS == ARITHS
+    for case, label in forms.CASE_LABELS.items():
+        assert forms.reaches(label, case), (case, label)
+        if label != "c.edge":                                              # reaches() tells the forms apart (the channel edges run at map sizes of their own)
+            assert not any(forms.reaches(other, case) for other in ("tile.edge", "nt.switch", "rows.all", "ties.cross", "eps.clamp", "nan.cell", "c.edge") if other != label), case
+    by = lambda label: [c for c, l in forms.CASE_LABELS.items() if l == label]
+    assert {c[1] for c in by("tile.edge")} == {32, 33, 64, 65, 96, 97} and any(c[0] % -(-c[1] // 32) for c in by("tile.edge"))
+    assert {c[1] for c in by("nt.switch")} == {128, 129, 160, 255}
+    assert {c[1] for c in by("rows.all")} == {256, 129, 33} and {c[2] for c in by("c.edge")} == {4, 12, 24, 8, do.MATCH_MAX_C}
+    assert all(c[3] == ("plain" if c[2] == do.MATCH_MAX_C else "signed") for c in by("c.edge"))
+    # a permutation of 256 cells wins at every (wave, t, half, r) exactly once
+    assert len({forms.position(j) for j in range(256)}) == 256 == 4 * 2 * 2 * 16
+    assert [forms.position(j)[:2] for j in (5, 37, 133, 165, 130, 100)] == [(0, 0), (1, 0), (0, 1), (1, 1), (0, 1), (3, 0)]
+    from ssv_amd import _lib
+    assert (do.MATCH_MAX_S, do.MATCH_MAX_C) == (_lib.DENSE_MATCH_MAX_S, _lib.DENSE_MATCH_MAX_C)
+    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "densecl.hip")).read()
+    assert "if (s <= 128) SSV_DM(1, true); else SSV_DM(2, true);" in src and "const bool work = 32 * wave < s;" in src and "32 * (wave + 4 * t) + row" in src
+    doc = forms.documented_labels()
+    assert len(doc) == 9 and set(doc.values()) == {"ssv_dense_match"}
+    used = {b for labels in forms.TARGETS.values() for b in labels.split()}
+    assert set(doc) == used and set(forms.TARGETS) == {name for name in dir(forms) if name.startswith("test_")}
+
+
+@pytest.mark.parametrize("seed", do.MATCH_SEEDS)
+@pytest.mark.parametrize("case", do.FORM_MATCH_CASES, ids=do.match_id)
+def test_match_form_cases_keep_the_fp32_reference_meaningful(case, seed):
+    """As for MATCH_CASES: the fp32 oracle picks the fp64 arg-max in every cell and the smallest fp64 cosine gap is at least 1e-6 (planted copies count as their
+    original; the NaN cell has no gap); and the conditions of the planted variants"""
+    ins = do.make_match_case(case, seed)
+    f1, f2 = ins[:2]
+    b, s, c, variant = case
+    eps = do.match_eps(case)
+    assert f1.shape == f2.shape == (b, s, c) and len(ins) == (3 if variant == "eps" else 2) and (variant != "eps" or ins[2] == eps == 0.5)
+    r64, r32 = do.dense_match(f1, f2, eps), do.dense_match(f1, f2, eps, dtype=torch.float32)
+    gap = do.match_gap(case, r64)
+    print(f"{do.match_id(case)} seed {seed}: smallest gap {gap:.3g}")
+    assert torch.equal(r64["j"], r32["j"]) and gap >= 1e-6
+    if variant == "signed":
+        assert float(f1.min()) < 0.0 and float(f2.min()) < 0.0 and float(f2.abs().sum(dim=2).min()) > 0.0
+    if variant == "perm":
+        p = do.match_perm(case, seed)
+        assert all(sorted(row) == list(range(s)) for row in p.tolist()) and torch.equal(r64["j"], p) and gap >= 0.1
+        assert float((r64["sim"] - 1.0).abs().max()) < 1e-12
+    if variant == "ties":
+        for ref, dt in ((r64, torch.float64), (r32, torch.float32)):
+            for copy, orig in do.TIES.items():
+                assert torch.equal(ref["score"][0, :, copy].view(torch.int64 if dt == torch.float64 else torch.int32),
+                                   ref["score"][0, :, orig].view(torch.int64 if dt == torch.float64 else torch.int32)), (copy, orig)
+            assert [int(ref["j"][0, cell]) for cell in (0, 40, 1, 255)] == [5, 5, 100, 100]
+            assert not bool(torch.isin(ref["j"][0], torch.tensor(list(do.TIES))).any())
+    if variant == "eps":
+        loose = do.dense_match(f1, f2, 1e-12)
+        share = float((loose["j"] != r64["j"]).double().mean())
+        print(f"{do.match_id(case)} seed {seed}: the clamp changes the arg-max in {100 * share:.1f} % of the cells")
+        assert share >= 0.25 and not bool((r64["j"] % 2 == 0).any())
+        assert float(f2[:, ::2].double().norm(dim=2).max()) < eps < float(f2[:, 1::2].double().norm(dim=2).min())
+    if variant == "nan":
+        n, i, ch = do.NAN_CELL
+        assert bool(torch.isnan(f1[n, i, ch])) and int(torch.isnan(f1).sum()) == 1 and not bool(torch.isnan(f2).any())
+        assert int(r64["idx"][n, i]) == n * s + 0 and bool(torch.isnan(r64["sim"][n, i])) and int(torch.isnan(r64["sim"]).sum()) == 1
+
+
+def test_the_densecl_forms_accuracy_bounds_are_what_the_committed_report_implies():
+    """FACTOR of tests/test_gpu_dense_nce_forms.py and of tests/test_gpu_dense_match_forms.py = the worst measured ratio of their family in
+    profiles/densecl_forms_report.json rounded up to the next power of two, never above 8; every case, arithmetic and output is in the report; the older
+    table's FACTOR is untouched"""
+    import forms_report as fr
+    import test_gpu_dense_match_forms as mforms
+    import test_gpu_dense_nce_forms as qforms
+    doc = json.load(open(os.path.join(ROOT, "profiles", "densecl_forms_report.json")))
+    for forms, name, ids, outs in ((qforms, "dense_nce.forms", [do.case_id(c) for c in do.FORM_CASES], {"loss", "lse", "dq"}),
+                                   (mforms, "dense_match.forms", [do.match_id(c) for c in do.FORM_MATCH_CASES], {"sim"})):
+        fam = doc["families"][name]
+        worst = max(fam["worst_e_ratio"], fam["worst_m_ratio"])
+        assert worst <= 8.0 and fam["FLOOR"] == forms.FLOOR <= 16 * fr.U and forms.FACTOR == fr.next_pow2(worst) == fam["FACTOR"] == fam["FACTOR_implied"], name
+        assert set(doc["cases"][name]) == {f"{i}[{a}]" for i in ids for a in ARITHS}
+        assert all(set(t) == outs for t in doc["cases"][name].values())
+    assert set(doc["match_cells"]) == set(doc["cases"]["dense_match.forms"]) and all(v["excused"] <= 0.01 * v["cells"] for v in doc["match_cells"].values())
+    assert re.fullmatch(r"[0-9a-f]{16}", doc["source_sha16"]) and do.FACTOR == 8.0 and do.FLOOR == 2 * fr.U
