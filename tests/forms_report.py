@@ -2,7 +2,8 @@
 outputs, guarded device buffers, and the report both files write into under SSV_KMEANS_PIRL_REPORT=<path> (profiles/kmeans_pirl_forms_report.json).  The
 nearest-neighbour lookup, ProtoNCE and whitening form tests share it too and write profiles/lookup_loss_forms_report.json under SSV_LOOKUP_LOSS_FORMS_REPORT.
 The DenseCL form tests (tests/test_gpu_dense_nce_forms.py, tests/test_gpu_dense_match_forms.py) write a third report, profiles/densecl_forms_report.json, under
-SSV_DENSECL_FORMS_REPORT.
+SSV_DENSECL_FORMS_REPORT.  The augmentation form tests (tests/test_gpu_augment_forms.py) take the guarded buffers alone: they compare bits, not errors, and write
+profiles/augment_forms_report.json themselves.
 
 Rule (a): with ref64 the plain reference in float64, ref32 the SAME lines in float32, e(x) = ||x - ref64||_2 / ||ref64||_2 and m(x) = max|x - ref64| / max|ref64|,
     e(got) <= FACTOR * e(ref32) + FLOOR     and the same for m;
