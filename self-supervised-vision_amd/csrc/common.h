@@ -69,6 +69,16 @@ __device__ __forceinline__ float wave_max(float v) {
 
 static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }           // workspace sections start on 256-byte boundaries
 
+// whether no output is an input or another output; a null output (an optional one the caller left out) is skipped
+static inline bool no_alias(const void* const* out, int no, const void* const* in, int ni) {
+  for (int a = 0; a < no; ++a) {
+    if (!out[a]) continue;
+    for (int b = 0; b < ni; ++b) if (out[a] == in[b]) return false;
+    for (int b = a + 1; b < no; ++b) if (out[a] == out[b]) return false;
+  }
+  return true;
+}
+
 // the 1x1 "convolution" that is the GEMM Y[rows, K] = X[rows, C] W[K, C]^T (w_planes: W pre-split by ssv_split_planes, or null)
 static inline ssv_conv_desc gemm_conv_desc(int rows, int C, int K, int arithmetic, const void* w_planes = nullptr) {
   ssv_conv_desc cd = {};

@@ -9,7 +9,7 @@
 //
 // ssv_queue_nce: InfoNCE of every query against a queue, with one positive per query gathered from another matrix.  The queue carries no gradient, so the loss
 //   and d loss / d q are one pass of the shape of a flash-attention forward.
-//   * SSV_ARITH_BF16X3, d % 32 == 0, d <= SSV_QUEUE_NCE_FUSED_MAX_D: FUSED (qn_fused_k): pn_fused_k's pass (csrc/protonce.hip) with one temperature - bank rows
+//   * SSV_ARITH_BF16X3, d % 32 == 0, d <= SSV_QUEUE_NCE_FUSED_MAX_D: FUSED (qn_fused_k): the pass of csrc/bank_softmax_pass.h (described in csrc/protonce.hip) with the source Range, one temperature - bank rows
 //     streamed in fp32 and split in registers as the A operand, the queries split once per call into fragment order (qn_prep_k) as the B operand, the second
 //     product out^T += V^T P^T under the online rescale with the tile of bank rows read back transposed from LDS in the order in which P lies in the accumulators.
 //     A workgroup owns one slice of the queue (L rows, a multiple of SSV_QUEUE_NCE_SLICE) and one block of KT query tiles; its four waves take the four quarters
@@ -25,32 +25,22 @@
 //   a row's sum, its logarithm, its loss (with s+ from the unrounded dot product) and the mean over the rows are carried in double, so the loss takes one
 //   fp32 rounding at the end - with one query the loss is one row's, and fp32 steps there would each cost it half an ulp.
 // No floating-point atomics anywhere; every workspace value that is read was written by the same call.
-#include "common.h"
-#include "split_bf16.h"
-#include <math.h>
+#include "bank_softmax.h"
 
 namespace {
+
+using banksm::arith_ok;
+using banksm::mul_rn;
 
 constexpr int MATCH_MAX_S = SSV_DENSE_MATCH_MAX_S, MATCH_MAX_C = SSV_DENSE_MATCH_MAX_C;
 constexpr int SLICE = SSV_QUEUE_NCE_SLICE, MAX_SLICES = SSV_QUEUE_NCE_MAX_SLICES, FUSED_MAX_D = SSV_QUEUE_NCE_FUSED_MAX_D, TARGET_WGS = SSV_QUEUE_NCE_TARGET_WGS;
 constexpr int MAX_M = SSV_QUEUE_NCE_MAX_M, MAX_D = SSV_KNN_MAX_D;
-constexpr int CHUNK_ROWS = 1024;                      // query rows of one chunk of S (unfused)
-constexpr int64_t CHUNK_ELEMS = 1ll << 25;            // ... and its elements: fewer rows against a long queue
-constexpr float LOG2E = 1.4426950408889634f;
-
-// one fp32 multiply that stays one whatever the contraction default
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-
-bool arith_ok(int32_t a) { return a == SSV_ARITH_F32_MFMA || a == SSV_ARITH_BF16X3; }
 
 // ---- ssv_dense_match ---------------------------------------------------------------------------------------------------------------------------------------------
 // candidates are (score, dot, clamped norm, j): the higher score wins, equal scores go to the lower j
@@ -143,12 +133,11 @@ dm_match_k(int s, int c, int qtiles, const float* __restrict__ f1, const float* 
 }
 
 // ---- ssv_queue_nce: the plan -----------------------------------------------------------------------------------------------------------------------------------
-struct Plan {
+struct Plan : banksm::FusedPlan {
   bool fused;
-  int T, mpad, KT, DT, nsl;                           // fused: tiles of 32 queries, queries with the pad of the last tile, query tiles of a workgroup, d / 32, slices
-  int64_t L;                                          // fused: rows of one slice
+  int nsl; int64_t L;                                 // fused: slices, rows of one slice
   int cr; int64_t kp;                                 // unfused: query rows of a chunk, rows of the queue rounded up to 16
-  size_t rl_bytes, pm_bytes, pacc_bytes, planes_bytes, s_bytes, bpad_bytes;
+  size_t rl_bytes, s_bytes, bpad_bytes;
   size_t total() const { return rl_bytes + 2 * pm_bytes + pacc_bytes + planes_bytes + s_bytes + bpad_bytes; }
 };
 
@@ -164,8 +153,7 @@ Plan make_plan(int32_t m, int64_t K, int32_t d, int32_t arithmetic) {
   p.fused = is_fused(d, arithmetic);
   p.rl_bytes = up256((size_t)m * 8);                  // the rows' losses in double: the mean is rounded to fp32 once
   if (p.fused) {
-    p.T = cdiv(m, 32); p.mpad = p.T * 32; p.DT = d / 32;
-    p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;             // two query tiles at d >= 96 do not fit the register file (protonce.hip)
+    banksm::plan_tiles(p, m, d);
     const int blocks = cdiv(p.T, p.KT);
     int64_t want = cdiv(TARGET_WGS, blocks);            // slices only as far as a small m needs them
     if (want > MAX_SLICES) want = MAX_SLICES;
@@ -173,17 +161,11 @@ Plan make_plan(int32_t m, int64_t K, int32_t d, int32_t arithmetic) {
     if (want > units) want = units;
     p.L = (int64_t)SLICE * cdiv64(units, want);
     p.nsl = (int)cdiv64(K, p.L);
-    p.pm_bytes = up256((size_t)4 * p.nsl * p.mpad * 4);
-    p.pacc_bytes = up256((size_t)4 * p.nsl * p.mpad * d * 4);
-    p.planes_bytes = (size_t)3 * (d / 16) * p.T * 1024;
+    banksm::plan_bytes(p, p.nsl, d);
   } else {
     p.mpad = m;
     p.kp = (K + 15) / 16 * 16;
-    int64_t cr = CHUNK_ELEMS / p.kp;
-    if (cr > CHUNK_ROWS) cr = CHUNK_ROWS;
-    if (cr > m) cr = m;
-    if (cr < 1) cr = 1;
-    p.cr = (int)cr;
+    p.cr = banksm::chunk_rows(p.kp, m);
     p.s_bytes = up256((size_t)p.cr * p.kp * 4);
     p.bpad_bytes = up256((size_t)p.kp * d * 4);
   }
@@ -202,140 +184,25 @@ __global__ void __launch_bounds__(256) qn_loss_k(int n, const double* __restrict
 }
 
 // ---- fused -------------------------------------------------------------------------------------------------------------------------------------------------------
-// the queries' three planes in fragment order (pn_prep_k's layout): the 16 bytes lane l needs for (plane, slab, tile of 32 queries) sit at
-// ((plane * slabs + slab) * tiles + tile) * 64 + l; rows behind m are zeros
+// the queries' three planes in fragment order with d / 16 slabs (banksm::prep_planes); rows behind m are zeros
 __global__ void __launch_bounds__(256) qn_prep_k(int d, int m, int T, int NS, const float* __restrict__ q, u32x4* __restrict__ planes) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nfrag = NS * T;
-  const int u = blockIdx.x * 4 + wave;
-  if (u >= nfrag) return;
-  const int s = u / T, t = u % T, i = 32 * t + (lane & 31), col = 16 * s + 8 * (lane >> 5);
-  f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
-  if (i < m) {
-    const float* p = q + (int64_t)i * d + col;
-    a = *(const f32x4*)p;
-    b = *(const f32x4*)(p + 4);
-  }
-  bf16x8 pl[3];
-  splitbf::split8(a, b, pl);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) planes[((int64_t)k * nfrag + u) * 64 + lane] = __builtin_bit_cast(u32x4, pl[k]);
+  banksm::prep_planes<false>(d, m, T, NS, q, planes);
 }
 
-// float offset of column `col` of row `row` in a wave's tile of bank rows [32][D]: the 16-byte granules of a row are XOR-ed with the row's low three bits
-// (protonce.hip's vt_off: conflict-free for the writes of a granule column and for the transposed reads of one row)
-template <int D>
-__device__ __forceinline__ int vt_off(int row, int col) { return row * D + ((((col >> 2) ^ (row & 7)) << 2) | (col & 3)); }
-
+// the pass of bank_softmax_pass.h over one slice of the queue: rows [0, K), one temperature, the bare rows as V, the positive outside the bank (qn_fold_k adds it)
 template <int DT, int KT>
 __global__ void __launch_bounds__(256, 1)
 qn_fused_k(const float* __restrict__ bank, int64_t K, int64_t L, float inv_temp, int T, int mpad, int blocks, const u32x4* __restrict__ planes,
            float* __restrict__ pm, float* __restrict__ pl, float* __restrict__ pacc) {
-  constexpr int D = 32 * DT, NS = 2 * DT;
+  constexpr int D = 32 * DT;
   __shared__ float vt[4][32 * D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
   const int sl = blockIdx.x / blocks, tb = (blockIdx.x % blocks) * KT;
-  const int64_t nfrag = (int64_t)NS * T;
-  int tt[KT];                                                           // tiles behind the last repeat it (their results are not written)
-#pragma unroll
-  for (int t = 0; t < KT; ++t) tt[t] = min(tb + t, T - 1);
-  auto frag = [&](int s, int t, int q) { return __builtin_bit_cast(bf16x8, planes[(q * nfrag + (int64_t)s * T + tt[t]) * 64 + lane]); };
-  float mrun[KT], lrun[KT];
-  f32x16 out[KT][DT];
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    mrun[t] = -INFINITY; lrun[t] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) out[t][dt][r] = 0.f;
-  }
-  float* myv = vt[wave];
-  // the wave's quarter of the slice, 32 bank rows at a time (bounds are uniform over the wave: the matrix instructions run with all lanes)
-  const int64_t q0 = (int64_t)sl * L + (int64_t)wave * (L >> 2);
-  const int64_t q1 = q0 + (L >> 2) < K ? q0 + (L >> 2) : K;
-  for (int64_t r0 = q0; r0 < q1; r0 += 32) {
-    const int64_t brow = r0 + c < K ? r0 + c : K - 1;                   // rows behind the queue repeat its last one and are masked by index below
-    const float* bp = bank + brow * D + 8 * half;
-    f32x16 acc[KT];
-#pragma unroll
-    for (int t = 0; t < KT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    __builtin_amdgcn_wave_barrier();                                    // the previous tile's transposed reads are behind this tile's writes
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const f32x4 a = *(const f32x4*)(bp + 16 * s), b = *(const f32x4*)(bp + 16 * s + 4);
-      bf16x8 xb[3];
-      splitbf::split8(a, b, xb);
-      *(f32x4*)(myv + vt_off<D>(c, 16 * s + 8 * half)) = a;              // V = the bank rows themselves: inv_temp is applied once, in qn_fold_k
-      *(f32x4*)(myv + vt_off<D>(c, 16 * s + 8 * half + 4)) = b;
-#pragma unroll
-      for (int t = 0; t < KT; ++t) {
-        bf16x8 kf[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) kf[q] = frag(s, t, q);
-        splitbf::mma6_32(acc[t], xb, kf);                               // A: the bank rows (accumulator rows), B: the queries (one per lane)
-      }
-    }
-    bf16x8 pb[KT][2][3];
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      float sc[16], tm = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t j = r0 + splitbf::acc32_row(r, half);
-        sc[r] = j < K ? mul_rn(acc[t][r], inv_temp) : -INFINITY;        // the score: the product in the call's arithmetic, then ONE fp32 multiply
-        tm = fmaxf(tm, sc[r]);
-      }
-      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));                           // both halves of a query rescale the accumulators they share by the same factor
-      const float mn = fmaxf(mrun[t], tm);                              // finite from the first tile on: its first row is inside the queue
-      const float scale = __builtin_amdgcn_exp2f((mrun[t] - mn) * LOG2E);
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {                                    // the exponent from the UNROUNDED product (an fma)
-        sc[r] = sc[r] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(fmaf(acc[t][r], inv_temp, -mn) * LOG2E);
-        ps += sc[r];
-      }
-      lrun[t] = lrun[t] * scale + ps;
-      mrun[t] = mn;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[t][dt][r] *= scale;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        splitbf::split8(f32x4{sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]}, f32x4{sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]}, pb[t][u]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();                                    // the tile of V is complete before any lane reads a column of it
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = myv[vt_off<D>((i & 3) + 16 * u + 8 * (i >> 2) + 4 * half, 32 * dt + c)];   // P's own order: no shuffle on the B side
-        bf16x8 va[3];
-        splitbf::split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, va);
-#pragma unroll
-        for (int t = 0; t < KT; ++t) splitbf::mma6_32(out[t][dt], va, pb[t][u]);   // A: 32 columns of V, B: P of the queries
-      }
-  }
-  const int64_t part = (int64_t)sl * 4 + wave;
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    const float lt = lrun[t] + __shfl_xor(lrun[t], 32, 64);
-    if (tb + t >= T) continue;
-    const int64_t o = part * mpad + 32 * (tb + t) + c;
-    if (half == 0) { pm[o] = mrun[t]; pl[o] = lt; }
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *(f32x4*)(pacc + o * D + 32 * dt + 8 * g + 4 * half) = f32x4{out[t][dt][4 * g], out[t][dt][4 * g + 1], out[t][dt][4 * g + 2], out[t][dt][4 * g + 3]};
-  }
+  const int64_t end = K;
+  const auto slice0 = [&] { return (int64_t)sl * L; };                                     // evaluated where the pass needs it
+  using SRC = banksm::Range;
+  const SRC src = {nullptr, nullptr, nullptr, 0, 0, 0, inv_temp};
+#include "bank_softmax_pass.h"
 }
 
 // one wavefront per query: the partials in ascending order, then the positive as one more partial, the positive's row off
@@ -393,9 +260,7 @@ __global__ void __launch_bounds__(256) qn_fold_k(int m, int d, int mpad, int par
 // ---- unfused -----------------------------------------------------------------------------------------------------------------------------------------------------
 // rows [0, k) of the queue into dst [kp][d], zero rows behind k
 __global__ void __launch_bounds__(256) qn_pad_k(int64_t k, int64_t kp, int d4, const f32x4* __restrict__ src, f32x4* __restrict__ dst) {
-  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (u >= kp * d4) return;
-  dst[u] = u < k * d4 ? src[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+  banksm::pad_rows(k, kp, d4, src, dst);
 }
 
 // one wavefront per row of S [rows][ld] (queries from row0; `cols` queue rows): lse and the row's loss over the positive and the queue, S overwritten by
@@ -477,10 +342,7 @@ extern "C" int ssv_queue_nce(int32_t m, int32_t d, int64_t K, int64_t mk, const 
                 (uintptr_t)ws) & 15) == 0, "ssv_queue_nce: pointers must be 16-byte aligned");
   const void* in[5] = {q, keys, pos, bank, ws};
   const void* out[4] = {loss, lse, dq, flag};
-  for (int a = 0; a < 4; ++a) {
-    for (int b = 0; b < 5; ++b) SSV_REQUIRE(out[a] != in[b], "ssv_queue_nce: loss, lse, dq and flag alias neither each other nor an input or the workspace");
-    for (int b = a + 1; b < 4; ++b) SSV_REQUIRE(out[a] != out[b], "ssv_queue_nce: loss, lse, dq and flag alias neither each other nor an input or the workspace");
-  }
+  SSV_REQUIRE(no_alias(out, 4, in, 5), "ssv_queue_nce: loss, lse, dq and flag alias neither each other nor an input or the workspace");
   const Plan p = make_plan(m, K, d, arithmetic);
   SSV_REQUIRE(ws_bytes >= p.total(), "ssv_queue_nce: workspace %zu < %zu bytes", ws_bytes, p.total());
   hipStream_t s = (hipStream_t)stream;
@@ -500,12 +362,7 @@ extern "C" int ssv_queue_nce(int32_t m, int32_t d, int64_t K, int64_t mk, const 
     const int NS = d / 16, blocks = cdiv(p.T, p.KT);
     hipLaunchKernelGGL(qn_prep_k, dim3((unsigned)cdiv(NS * p.T, 4)), dim3(256), 0, s, d, m, p.T, NS, q, planes);
     SSV_CHECK_LAUNCH("qn_prep_k");
-#define SSV_QN(DT, KT) hipLaunchKernelGGL((qn_fused_k<DT, KT>), dim3((unsigned)(p.nsl * blocks)), dim3(256), 0, s, bank, K, p.L, inv_temp, p.T, p.mpad, blocks, \
-                                          (const u32x4*)planes, pm, pl, pacc)
-    if (p.DT == 4) SSV_QN(4, 1); else if (p.DT == 3) SSV_QN(3, 1);
-    else if (p.DT == 2) { if (p.KT == 1) SSV_QN(2, 1); else SSV_QN(2, 2); }
-    else { if (p.KT == 1) SSV_QN(1, 1); else SSV_QN(1, 2); }
-#undef SSV_QN
+    SSV_FUSED_LADDER(qn_fused_k, p, dim3((unsigned)(p.nsl * blocks)), s, bank, K, p.L, inv_temp, p.T, p.mpad, blocks, (const u32x4*)planes, pm, pl, pacc);
     SSV_CHECK_LAUNCH("qn_fused_k");
     hipLaunchKernelGGL(qn_fold_k, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, s, m, d, p.mpad, 4 * p.nsl, mk, (const float*)pm, (const float*)pl, (const float*)pacc,
                        q, keys, pos, inv_temp, inv_temp * inv, lse, rl, dq, flag);

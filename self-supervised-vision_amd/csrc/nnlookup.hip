@@ -6,7 +6,7 @@
 //   * SSV_ARITH_BF16X3, d % 32 == 0, d <= SSV_NN_LOOKUP_FUSED_MAX_D: FUSED (nn_fused_k).  S = Q B^T never reaches memory.  The BANK is streamed in fp32 and
 //     split into the three bf16 planes in registers (csrc/split_bf16.h: split8), the way kmeans_fused_k streams x - no per-call re-split of a 100 MB queue - but as
 //     the A operand of v_mfma_f32_32x32x16_bf16 (lane l: bank row l & 31 of the tile, d = 16 s + 8 (l >> 5) + 0..7).  The QUERIES (m <= 8192: at most a few MB,
-//     L2-resident) are split once per call into fragment order (nn_prep_k, kmeans_prep_k's layout) and are the B operand, so a LANE owns a QUERY: element r of the
+//     L2-resident) are split once per call into fragment order (nn_prep_k: prep_planes of csrc/bank_softmax.h, kmeans_prep_k's layout) and are the B operand, so a LANE owns a QUERY: element r of the
 //     32 x 32 accumulator in lane (c, h) is the score of query c against bank row acc32_row(r, h) of the tile, and the arg-max over the bank is one compare-select
 //     per accumulator element INSIDE the lane - no column-wise reduction over the tile.  A workgroup owns one slice of the bank (SSV_NN_LOOKUP_SLICE rows; a
 //     multiple of it above 2^21 rows) and one block of KT <= 8 query tiles (256 queries): its four waves take the four quarters of the slice, 32 rows at a time, and
@@ -16,15 +16,15 @@
 //     workspace, one wavefront per row (nn_rowarg_k, the pattern of kmeans_rowarg_k) which folds the part into the running best; then nn_fold_k.
 //   Every bank row runs ONE instruction sequence on either route whatever its position (a row of the A operand / a column of the GEMM), so bit-identical rows score
 //   bit-identically and a duplicate never beats its first copy.  Rows behind n are never read: the fused kernel repeats row n - 1 and masks by index.
-#include "common.h"
-#include "split_bf16.h"
-#include <math.h>
+#include "bank_softmax.h"
 
 namespace {
 
+using banksm::arith_ok;
+
 constexpr int SLICE = SSV_NN_LOOKUP_SLICE, MAX_SLICES = SSV_NN_LOOKUP_MAX_SLICES, FUSED_MAX_D = SSV_NN_LOOKUP_FUSED_MAX_D;
 constexpr int MAX_M = SSV_NN_LOOKUP_MAX_M, MAX_D = SSV_KNN_MAX_D;
-constexpr int CHUNK_ROWS = 1024;                                         // query rows of one chunk of S (unfused)
+constexpr int CHUNK_ROWS = 1024;                                         // query rows of one chunk of S (unfused).  This file's own rule, not banksm::chunk_rows: the bank is cut into parts here, so there is no element cap
 constexpr int64_t PART_ELEMS = 1ll << 26, MAX_PART_COLS = 65536;          // one part of the bank on the unfused route: the partition of ssv_knn_search
 
 struct Plan {
@@ -58,24 +58,9 @@ Plan make_plan(int32_t m, int64_t n, int32_t d, int32_t arithmetic) {
   return p;
 }
 
-// the queries' three planes in fragment order: the 16 bytes lane l needs for (plane, slab, tile of 32 queries) sit at ((plane * slabs + slab) * tiles + tile) * 64 + l
-// (one (slab, tile) per wave); rows behind m and columns behind d are zeros
+// the queries' three planes in fragment order with S4 slabs (banksm::prep_planes): S4 is a multiple of 4, so the slabs behind d are there and hold zeros
 __global__ void __launch_bounds__(256) nn_prep_k(int d, int m, int T, int S4, const float* __restrict__ q, u32x4* __restrict__ planes) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nfrag = S4 * T;
-  const int u = blockIdx.x * 4 + wave;
-  if (u >= nfrag) return;
-  const int s = u / T, t = u % T, i = 32 * t + (lane & 31), col = 16 * s + 8 * (lane >> 5);
-  f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
-  if (i < m) {
-    const float* p = q + (int64_t)i * d + col;
-    if (col < d) a = *(const f32x4*)p;
-    if (col + 4 < d) b = *(const f32x4*)(p + 4);
-  }
-  bf16x8 pl[3];
-  splitbf::split8(a, b, pl);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) planes[((int64_t)k * nfrag + u) * 64 + lane] = __builtin_bit_cast(u32x4, pl[k]);
+  banksm::prep_planes<true>(d, m, T, S4, q, planes);
 }
 
 template <int KT>
@@ -226,24 +211,20 @@ __global__ void __launch_bounds__(256) nn_fold_k(int m, int d, int P, int mpad, 
 }  // namespace
 
 extern "C" size_t ssv_nn_lookup_workspace_bytes(int32_t m, int64_t n, int32_t d, int32_t arithmetic) {
-  if (!shape_ok(m, n, d) || (arithmetic != SSV_ARITH_F32_MFMA && arithmetic != SSV_ARITH_BF16X3)) return 0;
+  if (!shape_ok(m, n, d) || !arith_ok(arithmetic)) return 0;
   return make_plan(m, n, d, arithmetic).total();
 }
 
 extern "C" int ssv_nn_lookup(int32_t m, int64_t n, int32_t d, const float* queries, const float* bank, float out_scale, float* nn, int32_t* idx, float* sim,
                              int32_t arithmetic, void* ws, size_t ws_bytes, void* stream) {
   SSV_REQUIRE(shape_ok(m, n, d), "ssv_nn_lookup: need 1 <= m <= %d, 1 <= n < 2^31, d %% 4 == 0, 4 <= d <= %d (got m=%d n=%lld d=%d)", MAX_M, MAX_D, m, (long long)n, d);
-  SSV_REQUIRE(arithmetic == SSV_ARITH_F32_MFMA || arithmetic == SSV_ARITH_BF16X3, "ssv_nn_lookup: unknown arithmetic %d", arithmetic);
+  SSV_REQUIRE(arith_ok(arithmetic), "ssv_nn_lookup: unknown arithmetic %d", arithmetic);
   SSV_REQUIRE(isfinite(out_scale), "ssv_nn_lookup: out_scale must be finite (got %g)", (double)out_scale);
   SSV_REQUIRE(queries && bank && idx && sim && ws, "ssv_nn_lookup: null pointer (only nn may be NULL)");
   SSV_REQUIRE((((uintptr_t)queries | (uintptr_t)bank | (uintptr_t)nn | (uintptr_t)idx | (uintptr_t)sim | (uintptr_t)ws) & 15) == 0, "ssv_nn_lookup: pointers must be 16-byte aligned");
   const void* in[3] = {queries, bank, ws};
   const void* out[3] = {idx, sim, nn};
-  for (int a = 0; a < 3; ++a) {
-    if (!out[a]) continue;
-    for (int b = 0; b < 3; ++b) SSV_REQUIRE(out[a] != in[b], "ssv_nn_lookup: nn, idx and sim alias neither each other nor an input or the workspace");
-    for (int b = a + 1; b < 3; ++b) SSV_REQUIRE(out[a] != out[b], "ssv_nn_lookup: nn, idx and sim alias neither each other nor an input or the workspace");
-  }
+  SSV_REQUIRE(no_alias(out, 3, in, 3), "ssv_nn_lookup: nn, idx and sim alias neither each other nor an input or the workspace");
   const Plan p = make_plan(m, n, d, arithmetic);
   SSV_REQUIRE(ws_bytes >= p.total(), "ssv_nn_lookup: workspace %zu < %zu bytes", ws_bytes, p.total());
   hipStream_t s = (hipStream_t)stream;

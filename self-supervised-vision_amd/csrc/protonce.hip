@@ -3,7 +3,8 @@
 // d loss / d q together are ONE pass of the shape of a flash-attention forward: scores S = (Q C^T) o inv_phi, values V = inv_phi o C, output softmax(S) V minus
 // the positive's row of V.
 //
-//   * SSV_ARITH_BF16X3, d % 32 == 0, d <= SSV_PROTO_NCE_FUSED_MAX_D: FUSED (pn_fused_k).  S and P never reach memory.  The operand plan is nn_fused_k's
+//   * SSV_ARITH_BF16X3, d % 32 == 0, d <= SSV_PROTO_NCE_FUSED_MAX_D: FUSED (pn_fused_k).  S and P never reach memory.  The pass is written once, as the text of csrc/bank_softmax_pass.h
+//     (included here with the source Segments; qn_fused_k of csrc/densecl.hip includes it with the source Range), and described here.  The operand plan is nn_fused_k's
 //     (csrc/nnlookup.hip): the prototypes are streamed in fp32 and split in registers as the A operand of v_mfma_f32_32x32x16_bf16, the queries are split once
 //     per call into fragment order (pn_prep_k) and are the B operand, so a LANE owns a QUERY: element r of the score tile in lane (c, h) is query c against
 //     prototype acc32_row(r, h) of the tile, and the running max and sum are compare, exp and add inside the lane (one exchange with lane ^ 32 per tile for the
@@ -24,23 +25,15 @@
 //     overwrites S with d loss / d S (pn_row_k), ssv_conv2d_dgrad accumulates dq.  The softmax-CE kernel of the linear probe returns a mean and no lse, so the
 //     row kernel is this file's own.
 // No floating-point atomics anywhere; every workspace value that is read was written by the same call.
-#include "common.h"
-#include "split_bf16.h"
-#include <math.h>
+#include "bank_softmax.h"
 
 namespace {
 
+using banksm::arith_ok;
+using banksm::mul_rn;
+
 constexpr int SLICE = SSV_PROTO_NCE_SLICE, MAX_SLICES = SSV_PROTO_NCE_MAX_SLICES, FUSED_MAX_D = SSV_PROTO_NCE_FUSED_MAX_D;
 constexpr int MAX_M = SSV_PROTO_NCE_MAX_M, MAX_SEGS = SSV_PROTO_NCE_MAX_SEGS, MAX_D = SSV_KNN_MAX_D;
-constexpr int CHUNK_ROWS = 1024;                      // query rows of one chunk of S (unfused)
-constexpr int64_t CHUNK_ELEMS = 1ll << 25;            // ... and its elements: fewer rows against a long segment
-constexpr float LOG2E = 1.4426950408889634f;
-
-// one fp32 multiply that stays one whatever the contraction default: where this file wants the exact product inside a subtraction it writes the fma itself
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 struct SegTab {                                       // by value into every kernel: no table in device memory, nothing to upload
   int begin[MAX_SEGS], end[MAX_SEGS];                 // prototype rows [begin, end) of the segment
@@ -48,19 +41,17 @@ struct SegTab {                                       // by value into every ker
   int segs;
 };
 
-struct Plan {
+struct Plan : banksm::FusedPlan {
   bool fused;
-  int T, mpad, KT, DT;                                // fused: tiles of 32 queries, queries with the pad of the last tile, query tiles of a workgroup, d / 32
   int64_t max_slices;                                 // fused: slices of the worst segmentation of ktot rows into segs segments
   int cr; int64_t kp;                                 // unfused: query rows of a chunk, rows of the longest possible segment rounded up to 16
-  size_t spos_bytes, rl_bytes, pm_bytes, pacc_bytes, planes_bytes, s_bytes, cpad_bytes;
+  size_t spos_bytes, rl_bytes, s_bytes, cpad_bytes;
   size_t total() const { return spos_bytes + rl_bytes + 2 * pm_bytes + pacc_bytes + planes_bytes + s_bytes + cpad_bytes; }
 };
 
 bool shape_ok(int32_t m, int64_t ktot, int32_t d, int32_t segs) {
   return m >= 1 && m <= MAX_M && segs >= 1 && segs <= MAX_SEGS && ktot >= segs && ktot < (1ll << 31) && d >= 4 && d <= MAX_D && d % 4 == 0;
 }
-bool arith_ok(int32_t a) { return a == SSV_ARITH_F32_MFMA || a == SSV_ARITH_BF16X3; }
 
 Plan make_plan(int32_t m, int64_t ktot, int32_t d, int32_t segs, int32_t arithmetic) {
   Plan p = {};
@@ -68,21 +59,14 @@ Plan make_plan(int32_t m, int64_t ktot, int32_t d, int32_t segs, int32_t arithme
   p.spos_bytes = up256((size_t)segs * ((m + 31) / 32 * 32) * 4);
   p.rl_bytes = up256((size_t)segs * m * 4);
   if (p.fused) {
-    p.T = cdiv(m, 32); p.mpad = p.T * 32; p.DT = d / 32;
-    p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;             // two query tiles at d >= 96 do not fit the register file (the compiler's report: spills)
+    banksm::plan_tiles(p, m, d);
     const int64_t by_rows = cdiv64(ktot, SLICE) + segs, by_cap = (int64_t)MAX_SLICES * segs;
     p.max_slices = by_rows < by_cap ? by_rows : by_cap;
-    p.pm_bytes = up256((size_t)4 * p.max_slices * p.mpad * 4);
-    p.pacc_bytes = up256((size_t)4 * p.max_slices * p.mpad * d * 4);
-    p.planes_bytes = (size_t)3 * (d / 16) * p.T * 1024;
+    banksm::plan_bytes(p, p.max_slices, d);
   } else {
     p.mpad = m;
     p.kp = (ktot - (segs - 1) + 15) / 16 * 16;
-    int64_t cr = CHUNK_ELEMS / p.kp;
-    if (cr > CHUNK_ROWS) cr = CHUNK_ROWS;
-    if (cr > m) cr = m;
-    if (cr < 1) cr = 1;
-    p.cr = (int)cr;
+    p.cr = banksm::chunk_rows(p.kp, m);
     p.s_bytes = up256((size_t)p.cr * p.kp * 4);
     p.cpad_bytes = up256((size_t)p.kp * d * 4);
   }
@@ -118,156 +102,29 @@ __global__ void __launch_bounds__(256) pn_loss_k(int n, const float* __restrict_
 }
 
 // ---- fused ---------------------------------------------------------------------------------------------------------------------------------------------------
-// the queries' three planes in fragment order (nn_prep_k's layout with d / 16 slabs): the 16 bytes lane l needs for (plane, slab, tile of 32 queries) sit at
-// ((plane * slabs + slab) * tiles + tile) * 64 + l; rows behind m are zeros
+// the queries' three planes in fragment order with d / 16 slabs (banksm::prep_planes); rows behind m are zeros
 __global__ void __launch_bounds__(256) pn_prep_k(int d, int m, int T, int NS, const float* __restrict__ q, u32x4* __restrict__ planes) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nfrag = NS * T;
-  const int u = blockIdx.x * 4 + wave;
-  if (u >= nfrag) return;
-  const int s = u / T, t = u % T, i = 32 * t + (lane & 31), col = 16 * s + 8 * (lane >> 5);
-  f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
-  if (i < m) {
-    const float* p = q + (int64_t)i * d + col;
-    a = *(const f32x4*)p;
-    b = *(const f32x4*)(p + 4);
-  }
-  bf16x8 pl[3];
-  splitbf::split8(a, b, pl);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) planes[((int64_t)k * nfrag + u) * 64 + lane] = __builtin_bit_cast(u32x4, pl[k]);
+  banksm::prep_planes<false>(d, m, T, NS, q, planes);
 }
 
-// float offset of column `col` of row `row` in a wave's tile of scaled prototypes [32][D]: the 16-byte granules of a row are XOR-ed with the row's low three
-// bits, so the 32 lanes that write one granule column of 32 rows spread over 8 granules, and the 32 lanes that read 32 consecutive columns of ONE row still
-// touch 32 distinct banks (the XOR permutes granules inside an aligned group of 8 = 32 floats)
-template <int D>
-__device__ __forceinline__ int vt_off(int row, int col) { return row * D + ((((col >> 2) ^ (row & 7)) << 2) | (col & 3)); }
-
+// the pass of bank_softmax_pass.h over one slice of one segment: the slice's segment from the table, then the pass with the segment's scales, labels and positives
 template <int DT, int KT>
 __global__ void __launch_bounds__(256, 1)
 pn_fused_k(const float* __restrict__ protos, const float* __restrict__ inv_phi, const int32_t* __restrict__ labels, SegTab tab, int m, int T, int mpad,
            const u32x4* __restrict__ planes, float* __restrict__ pm, float* __restrict__ pl, float* __restrict__ pacc, float* __restrict__ spos) {
-  constexpr int D = 32 * DT, NS = 2 * DT;
+  constexpr int D = 32 * DT;
   __shared__ float vt[4][32 * D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
   const int tb = blockIdx.y * KT, sl = blockIdx.x;
   int seg = 0;
 #pragma unroll
   for (int k = 1; k < MAX_SEGS; ++k) seg = (k < tab.segs && sl >= tab.first[k]) ? k : seg;
-  const int64_t seg_b = tab.begin[seg], seg_e = tab.end[seg], L = tab.rows[seg];
-  const int64_t nfrag = (int64_t)NS * T;
-  int tt[KT], labg[KT];                                                 // tiles behind the last repeat it (their results are not written)
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    tt[t] = min(tb + t, T - 1);
-    const int i = 32 * tt[t] + c;
-    const int lab = i < m ? labels[(int64_t)seg * m + i] : -1;
-    labg[t] = (unsigned)lab < (unsigned)(seg_e - seg_b) ? (int)seg_b + lab : -1;       // a label outside the segment matches no row (pn_check_k reports it)
-  }
-  auto frag = [&](int s, int t, int q) { return __builtin_bit_cast(bf16x8, planes[(q * nfrag + (int64_t)s * T + tt[t]) * 64 + lane]); };
-  float mrun[KT], lrun[KT];
-  f32x16 out[KT][DT];
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    mrun[t] = -INFINITY; lrun[t] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) out[t][dt][r] = 0.f;
-  }
-  float* myv = vt[wave];
-  // the wave's quarter of the slice, 32 prototypes at a time (bounds are uniform over the wave: the matrix instructions run with all lanes)
-  const int64_t q0 = seg_b + (int64_t)(sl - tab.first[seg]) * L + (int64_t)wave * (L >> 2);
-  const int64_t q1 = q0 + (L >> 2) < seg_e ? q0 + (L >> 2) : seg_e;
-  for (int64_t r0 = q0; r0 < q1; r0 += 32) {
-    const int64_t brow = r0 + c < seg_e ? r0 + c : seg_e - 1;           // rows behind the segment repeat its last one and are masked by index below
-    const float* bp = protos + brow * D + 8 * half;
-    const float ipr = inv_phi[brow];
-    f32x16 acc[KT];
-#pragma unroll
-    for (int t = 0; t < KT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    __builtin_amdgcn_wave_barrier();                                    // the previous tile's transposed reads are behind this tile's writes
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const f32x4 a = *(const f32x4*)(bp + 16 * s), b = *(const f32x4*)(bp + 16 * s + 4);
-      bf16x8 xb[3];
-      splitbf::split8(a, b, xb);
-      *(f32x4*)(myv + vt_off<D>(c, 16 * s + 8 * half)) = a * ipr;        // V = inv_phi o C: one fp32 multiply, the one pn_fold_k repeats for the positive's row
-      *(f32x4*)(myv + vt_off<D>(c, 16 * s + 8 * half + 4)) = b * ipr;
-#pragma unroll
-      for (int t = 0; t < KT; ++t) {
-        bf16x8 kf[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) kf[q] = frag(s, t, q);
-        splitbf::mma6_32(acc[t], xb, kf);                               // A: the prototypes (accumulator rows), B: the queries (one per lane)
-      }
-    }
-    float ipj[16];                                                      // inv_phi of the 16 prototypes this lane holds scores of
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ipj[r] = __shfl(ipr, splitbf::acc32_row(r, half), 64);
-    bf16x8 pb[KT][2][3];
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      float sc[16], tm = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t j = r0 + splitbf::acc32_row(r, half);
-        const float v = mul_rn(acc[t][r], ipj[r]);                   // the score: the product in the call's arithmetic, then ONE fp32 multiply (never contracted into the subtraction below)
-        if (j == (int64_t)labg[t] && tb + t < T) spos[(int64_t)seg * mpad + 32 * tt[t] + c] = v;
-        sc[r] = j < seg_e ? v : -INFINITY;
-        tm = fmaxf(tm, sc[r]);
-      }
-      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));                           // both halves of a query rescale the accumulators they share by the same factor
-      const float mn = fmaxf(mrun[t], tm);                              // finite from the first tile on: its first row is inside the segment
-      const float scale = __builtin_amdgcn_exp2f((mrun[t] - mn) * LOG2E);
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {                                    // the exponent from the UNROUNDED product (an fma): the rounding of a score at |s| ~ 20 would cost p 1e-6
-        sc[r] = sc[r] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(fmaf(acc[t][r], ipj[r], -mn) * LOG2E);
-        ps += sc[r];
-      }
-      lrun[t] = lrun[t] * scale + ps;
-      mrun[t] = mn;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[t][dt][r] *= scale;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        splitbf::split8(f32x4{sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]}, f32x4{sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]}, pb[t][u]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();                                    // the tile of V is complete before any lane reads a column of it
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = myv[vt_off<D>((i & 3) + 16 * u + 8 * (i >> 2) + 4 * half, 32 * dt + c)];   // P's own order: no shuffle on the B side
-        bf16x8 va[3];
-        splitbf::split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, va);
-#pragma unroll
-        for (int t = 0; t < KT; ++t) splitbf::mma6_32(out[t][dt], va, pb[t][u]);   // A: 32 columns of V, B: P of the queries
-      }
-  }
-  const int64_t part = (int64_t)sl * 4 + wave;
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    const float lt = lrun[t] + __shfl_xor(lrun[t], 32, 64);
-    if (tb + t >= T) continue;
-    const int64_t o = part * mpad + 32 * (tb + t) + c;
-    if (half == 0) { pm[o] = mrun[t]; pl[o] = lt; }
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *(f32x4*)(pacc + o * D + 32 * dt + 8 * g + 4 * half) = f32x4{out[t][dt][4 * g], out[t][dt][4 * g + 1], out[t][dt][4 * g + 2], out[t][dt][4 * g + 3]};
-  }
+  const int64_t seg_b = tab.begin[seg], end = tab.end[seg], L = tab.rows[seg];
+  const auto slice0 = [&] { return seg_b + (int64_t)(sl - tab.first[seg]) * L; };      // evaluated where the pass needs it
+  const float* bank = protos;
+  using SRC = banksm::Segments;
+  const SRC src = {inv_phi, labels, spos, seg, seg_b, m, 0.f};
+#include "bank_softmax_pass.h"
 }
 
 // one wavefront per query: per segment the partials in ascending order, the positive's row off, then the segments in ascending order
@@ -320,9 +177,7 @@ __global__ void __launch_bounds__(256) pn_fold_k(SegTab tab, int m, int d, int m
 // ---- unfused -------------------------------------------------------------------------------------------------------------------------------------------------
 // rows [0, k) of a segment into dst [kp][d], zero rows behind k
 __global__ void __launch_bounds__(256) pn_pad_k(int64_t k, int64_t kp, int d4, const f32x4* __restrict__ src, f32x4* __restrict__ dst) {
-  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (u >= kp * d4) return;
-  dst[u] = u < k * d4 ? src[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+  banksm::pad_rows(k, kp, d4, src, dst);
 }
 
 // one wavefront per row of S [rows][ld] (queries from row0; `cols` prototypes of one segment): s = S o inv_phi, lse, the per-row loss, and S overwritten by
@@ -388,10 +243,7 @@ extern "C" int ssv_proto_nce(int32_t m, int32_t d, int32_t segs, const int64_t* 
                 (uintptr_t)ws) & 15) == 0, "ssv_proto_nce: pointers must be 16-byte aligned");
   const void* in[5] = {q, protos, inv_phi, labels, ws};
   const void* out[4] = {loss, lse, dq, flag};
-  for (int a = 0; a < 4; ++a) {
-    for (int b = 0; b < 5; ++b) SSV_REQUIRE(out[a] != in[b], "ssv_proto_nce: loss, lse, dq and flag alias neither each other nor an input or the workspace");
-    for (int b = a + 1; b < 4; ++b) SSV_REQUIRE(out[a] != out[b], "ssv_proto_nce: loss, lse, dq and flag alias neither each other nor an input or the workspace");
-  }
+  SSV_REQUIRE(no_alias(out, 4, in, 5), "ssv_proto_nce: loss, lse, dq and flag alias neither each other nor an input or the workspace");
   const Plan p = make_plan(m, ktot, d, segs, arithmetic);
   SSV_REQUIRE(ws_bytes >= p.total(), "ssv_proto_nce: workspace %zu < %zu bytes", ws_bytes, p.total());
   hipStream_t s = (hipStream_t)stream;
@@ -415,12 +267,8 @@ extern "C" int ssv_proto_nce(int32_t m, int32_t d, int32_t segs, const int64_t* 
     const int NS = d / 16, nsl = tab.first[segs];
     hipLaunchKernelGGL(pn_prep_k, dim3((unsigned)cdiv(NS * p.T, 4)), dim3(256), 0, s, d, m, p.T, NS, q, planes);
     SSV_CHECK_LAUNCH("pn_prep_k");
-#define SSV_PN(DT, KT) hipLaunchKernelGGL((pn_fused_k<DT, KT>), dim3((unsigned)nsl, (unsigned)cdiv(p.T, KT)), dim3(256), 0, s, protos, inv_phi, labels, tab, m, p.T, \
-                                          p.mpad, (const u32x4*)planes, pm, pl, pacc, spos)
-    if (p.DT == 4) SSV_PN(4, 1); else if (p.DT == 3) SSV_PN(3, 1);
-    else if (p.DT == 2) { if (p.KT == 1) SSV_PN(2, 1); else SSV_PN(2, 2); }
-    else { if (p.KT == 1) SSV_PN(1, 1); else SSV_PN(1, 2); }
-#undef SSV_PN
+    SSV_FUSED_LADDER(pn_fused_k, p, dim3((unsigned)nsl, (unsigned)cdiv(p.T, p.KT)), s, protos, inv_phi, labels, tab, m, p.T, p.mpad, (const u32x4*)planes, pm, pl,
+                     pacc, spos);
     SSV_CHECK_LAUNCH("pn_fused_k");
     hipLaunchKernelGGL(pn_fold_k, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, s, tab, m, d, p.mpad, (const float*)pm, (const float*)pl, (const float*)pacc,
                        (const float*)spos, protos, inv_phi, labels, inv, lse, rl, dq);

@@ -261,9 +261,12 @@ def test_plan_restatement_is_the_librarys():
     """densecl_oracle.plan against what the library exposes of its plan - the workspace size in both arithmetics - at every case and at shapes around each
     threshold; and the dispatch lines it restates"""
     from ssv_amd import _lib
-    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "densecl.hip")).read()
-    assert "p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;" in src and f"constexpr int CHUNK_ROWS = {do.CHUNK_ROWS};" in src and "CHUNK_ELEMS = 1ll << 25;" in src
-    assert "if (p.DT == 4) SSV_QN(4, 1); else if (p.DT == 3) SSV_QN(3, 1);" in src and "int64_t want = cdiv(TARGET_WGS, blocks);" in src
+    src, hdr = (open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", f)).read() for f in ("densecl.hip", "bank_softmax.h"))
+    # the tile rule, the chunk rule and the <DT, KT> ladder are written once, in the header; the file names them
+    assert "p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;" in hdr and f"constexpr int CHUNK_ROWS = {do.CHUNK_ROWS};" in hdr and "CHUNK_ELEMS = 1ll << 25;" in hdr
+    assert "if ((p).DT == 4) hipLaunchKernelGGL((KERNEL<4, 1>)" in hdr and "else if ((p).DT == 3) hipLaunchKernelGGL((KERNEL<3, 1>)" in hdr
+    assert "banksm::plan_tiles(p, m, d);" in src and "p.cr = banksm::chunk_rows(p.kp, m);" in src and "SSV_FUSED_LADDER(qn_fused_k, p," in src
+    assert "int64_t want = cdiv(TARGET_WGS, blocks);" in src
     assert "hipGetDeviceProperties" not in src and "ssv_device_cus" not in src            # the plan never asks the device for its size
     lib = _lib.load()
     shapes = [(c[0], c[2], c[1]) for c in do.cases()]

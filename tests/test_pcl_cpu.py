@@ -194,9 +194,11 @@ def test_plan_restatement_is_the_librarys():
     each threshold; and the dispatch lines it restates."""
     from ssv_amd import _lib
     assert (po.SLICE, po.MAX_SLICES, po.MAX_SEGS, po.FUSED_MAX_D) == (_lib.PROTO_NCE_SLICE, _lib.PROTO_NCE_MAX_SLICES, _lib.PROTO_NCE_MAX_SEGS, _lib.PROTO_NCE_FUSED_MAX_D)
-    src = open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", "protonce.hip")).read()
-    assert "p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;" in src and f"constexpr int CHUNK_ROWS = {po.CHUNK_ROWS};" in src and "CHUNK_ELEMS = 1ll << 25;" in src
-    assert "if (p.DT == 4) SSV_PN(4, 1); else if (p.DT == 3) SSV_PN(3, 1);" in src
+    src, hdr = (open(os.path.join(ROOT, "self-supervised-vision_amd", "csrc", f)).read() for f in ("protonce.hip", "bank_softmax.h"))
+    # the tile rule, the chunk rule and the <DT, KT> ladder are written once, in the header; the file names them
+    assert "p.KT = (p.T == 1 || p.DT >= 3) ? 1 : 2;" in hdr and f"constexpr int CHUNK_ROWS = {po.CHUNK_ROWS};" in hdr and "CHUNK_ELEMS = 1ll << 25;" in hdr
+    assert "if ((p).DT == 4) hipLaunchKernelGGL((KERNEL<4, 1>)" in hdr and "else if ((p).DT == 3) hipLaunchKernelGGL((KERNEL<3, 1>)" in hdr
+    assert "banksm::plan_tiles(p, m, d);" in src and "p.cr = banksm::chunk_rows(p.kp, m);" in src and "SSV_FUSED_LADDER(pn_fused_k, p," in src
     lib = _lib.load()
     shapes = [c[:3] for c in po.cases() + po.FORM_CASES]
     shapes += [(m, d, (300, 300)) for m in (1, 32, 33, 64, 65, 1024, 1025, 8192) for d in (32, 64, 96, 128, 132, 160, 4)]

@@ -69,7 +69,8 @@ def launches_by_scope(csrc_dir):
         for m in re.finditer(r'^(?:extern "C" |static |template <[^\n]*>\n)?[\w:<> \*]+\s+\**(\w+)\([^;{]*\)\s*\{\n(.*?)^\}', text, re.S | re.M):
             body = m.group(2)
             scopes = [c.lower() for c in re.findall(r"SSV_PROF_(\w+)", " ".join(re.findall(r"ProfScope ps\(([^;]+);", body)))]
-            kernels = [k + (t or "") for k, t in re.findall(r"hipLaunchKernelGGL\(\(?\s*(\w+)(<[^>]*>)?", body)]
+            # SSV_FUSED_LADDER (csrc/bank_softmax.h) launches the kernel template it is handed at every <DT, KT>
+            kernels = [k + (t or "") for k, t in re.findall(r"(?:hipLaunchKernelGGL\(\(?|SSV_FUSED_LADDER\()\s*(\w+)(<[^>]*>)?", body)]
             if scopes and kernels:
                 out.append((os.path.basename(f), m.group(1), scopes, kernels))
     return out
