@@ -1553,17 +1553,39 @@ def unpad_channels(t, out, accumulate=True):
     return out
 
 
-# ------------------------------------------------------------------------------------------- Winograd F(2x2, 3x3)
-def _wino_filter(w, wshape, transposed=False):
-    """U = G g G^T of the filter [K][3][3][C] - or, ``transposed``, of the rotated filter with the channel roles swapped (data gradient)."""
-    key = (w.data_ptr(), stream(), wshape, transposed, w._version)      # the version as _transposed_filter: an edited filter must miss
+# ------------------------------------------------------------------------------------------- Winograd F(2x2, 3x3) and F(4x4, 3x3)
+class _WinoForm:
+    """What the drivers of the two forms differ in: the transformed-domain positions, the names (the note's tag, the library's symbols: formed once, the drivers
+    run in the launch-bound regime) and whether ssv_<prefix>groups takes the statistics flag (F(4x4) groups by row of tiles or by image, F(2x2) always by 16 tiles)."""
+
+    def __init__(self, tag, prefix, positions, groups_takes_stats):
+        self.positions, self.groups_takes_stats = positions, groups_takes_stats
+        self.note_fwd, self.note_dgrad, self.note_wgrad = tag + "_fwd", tag + "_dgrad", tag + "_wgrad"
+        self.sym_tiles, self.sym_groups, self.sym_rows_per_group = prefix + "tiles", prefix + "groups", prefix + "stats_rows_per_group"
+        self.filter_transform, self.filter_grad = prefix + "filter_transform", prefix + "filter_grad"
+        self.input_transform, self.output_transform = prefix + "input_transform", prefix + "output_transform"
+
+    def tiles(self, n, h, w_):
+        return int(getattr(_lib.load(), self.sym_tiles)(n, h, w_))
+
+    def groups(self, n, h, w_, stats):
+        fn = getattr(_lib.load(), self.sym_groups)
+        return int(fn(n, h, w_, int(stats)) if self.groups_takes_stats else fn(n, h, w_))
+
+
+_F22, _F44 = _WinoForm("wino22", "ssv_wino_", 16, False), _WinoForm("wino44", "ssv_wino44_", 36, True)
+
+
+def _wino_filter(w, wshape, transposed=False, form=_F22):
+    """U = G g G^T of the filter [K][3][3][C] (16 or 36 positions) - or, ``transposed``, of the rotated filter with the channel roles swapped (data gradient)."""
+    key = (w.data_ptr(), stream(), wshape, transposed, form.positions, w._version)      # the version as _transposed_filter: an edited filter must miss
     hit = _WINO_U.get(key)
     if hit is not None:
         return hit[1]
     k, c, _, _ = wshape
     src, kk, cc = (w, k, c) if not transposed else (_transposed_filter(w, wshape), c, k)
-    u = torch.empty((16, kk, cc), dtype=torch.float32, device=w.device)
-    call("ssv_wino_filter_transform", kk, cc, ptr(src), ptr(u), stream())
+    u = torch.empty((form.positions, kk, cc), dtype=torch.float32, device=w.device)
+    call(form.filter_transform, kk, cc, ptr(src), ptr(u), stream())
     _WINO_U[key] = (w.untyped_storage(), u)
     return u
 
@@ -1712,20 +1734,6 @@ def _use_wino44(n, h, w_, c, k, max_ratio):
             and n * ((h + 3) // 4) * ((w_ + 3) // 4) >= WINOGRAD44_MIN_TILES)
 
 
-def _wino44_filter(w, wshape, transposed=False):
-    """U = G g G^T (6x6 positions) of the filter [K][3][3][C] - or, ``transposed``, of the rotated filter with the channel roles swapped (data gradient)."""
-    key = (w.data_ptr(), stream(), wshape, transposed, 44, w._version)      # the version as _transposed_filter: an edited filter must miss
-    hit = _WINO_U.get(key)
-    if hit is not None:
-        return hit[1]
-    k, c, _, _ = wshape
-    src, kk, cc = (w, k, c) if not transposed else (_transposed_filter(w, wshape), c, k)
-    u = torch.empty((36, kk, cc), dtype=torch.float32, device=w.device)
-    call("ssv_wino44_filter_transform", kk, cc, ptr(src), ptr(u), stream())
-    _WINO_U[key] = (w.untyped_storage(), u)
-    return u
-
-
 def _gemm_batched(nb, t, c, k, a, u, m):
     """m[b] = a[b] . u[b]^T for the nb transformed-domain positions (a [nb][t][c], u [nb][k][c], m [nb][t][k]); in the bf16x3 arithmetic on the planes of u."""
     if ARITHMETIC == "bf16x3" and c % 32 == 0 and k % 4 == 0:
@@ -1750,70 +1758,105 @@ def _gemm_batched_wgrad(nb, t, c, k, v, dm, du, chunk=0, flush=0):
         call("ssv_gemm_batched_wgrad", nb, t, c, k, ptr(v), ptr(dm), ptr(du), ptr(ws), ws.numel(), stream())
 
 
-def wino44_conv2d_fwd(x, w, in_affine=None, want_stats=False, keep_v=False):
-    """wino_conv2d_fwd through F(4x4, 3x3): 36 transformed-domain GEMMs over a quarter of the tiles.  ``keep_v``: the weight gradient's operand comes back as
-    the third result - the transformed input V [36][T][C] itself (WINOGRAD44_WGRAD: the weight gradient runs F(4x4) too), or the F(2x2) transformed input
-    [16][T2][C] the input transform then also leaves (wino_conv2d_wgrad tells them apart by the leading dimension).  Statistics partials: one per row of
-    tiles (H % 4 == 0) or per image."""
-    _note("wino44_fwd")
+def _wino_fwd(f, x, w, in_affine, want_stats, keep_v):
+    _note(f.note_fwd)
     _lib._dev(x, w)
     w, wshape = _ohwi(w)
     n, h, w_, c = x.shape
     k = wshape[0]
     lib = _lib.load()
-    t = int(lib.ssv_wino44_tiles(n, h, w_))
-    u = _wino44_filter(w, wshape)
+    t = f.tiles(n, h, w_)
+    u = _wino_filter(w, wshape, form=f)
     sc, sh = in_affine if in_affine is not None else (None, None)
-    v = torch.empty((36, t, c), dtype=torch.float32, device=x.device)
-    v2 = torch.empty((16, int(lib.ssv_wino_tiles(n, h, w_)), c), dtype=torch.float32, device=x.device) if (keep_v and not WINOGRAD44_WGRAD) else None
-    call("ssv_wino44_input_transform", n, h, w_, c, ptr(x), ptr(sc), ptr(sh), ptr(v), ptr(v2), stream())
-    if keep_v and WINOGRAD44_WGRAD:
-        v2 = v
-    m = torch.empty((36, t, k), dtype=torch.float32, device=x.device)
-    _gemm_batched(36, t, c, k, v, u, m)
+    v = torch.empty((f.positions, t, c), dtype=torch.float32, device=x.device)
+    v2 = None              # without its own weight gradient (round 4's selection) F(4x4)'s input transform also leaves the F(2x2) transformed input: that one is then kept
+    if f is _F44 and keep_v and not WINOGRAD44_WGRAD:
+        v2 = torch.empty((16, _F22.tiles(n, h, w_), c), dtype=torch.float32, device=x.device)
+    second = (ptr(v2),) if f is _F44 else ()
+    call(f.input_transform, n, h, w_, c, ptr(x), ptr(sc), ptr(sh), ptr(v), *second, stream())
+    m = torch.empty((f.positions, t, k), dtype=torch.float32, device=x.device)
+    _gemm_batched(f.positions, t, c, k, v, u, m)
     y = _empty((n, h, w_, k), x)
-    part = None
-    if want_stats:
-        part = _empty((2, int(lib.ssv_wino44_groups(n, h, w_, 1)), k), x)
-    call("ssv_wino44_output_transform", n, h, w_, k, ptr(m), ptr(y), None if part is None else ptr(part[0]), None if part is None else ptr(part[1]), None, stream())
-    rpg = int(lib.ssv_wino44_stats_rows_per_group(n, h, w_)) if want_stats else 0
-    return y, (None if part is None else (part[0], part[1], rpg)), v2
+    part = _empty((2, f.groups(n, h, w_, True), k), x) if want_stats else None
+    call(f.output_transform, n, h, w_, k, ptr(m), ptr(y), None if part is None else ptr(part[0]), None if part is None else ptr(part[1]), None, stream())
+    rpg = int(getattr(lib, f.sym_rows_per_group)(n, h, w_)) if want_stats else 0
+    return y, (None if part is None else (part[0], part[1], rpg)), ((v if v2 is None else v2) if keep_v else None)
 
 
-def wino44_conv2d_dgrad(dy, w, gate=None):
-    """wino_conv2d_dgrad through F(4x4, 3x3); the gate's partial sums come one per row of tiles.  ``dy`` may be the LazyGrad / tensor whose transformed input
-    the weight gradient's pass already wrote (`wino44_conv2d_wgrad`): the input transform is then skipped."""
-    _note("wino44_dgrad")
+def _wino_dgrad(f, dy, w, gate):
+    _note(f.note_dgrad)
     vd = None
-    if isinstance(dy, LazyGrad):
-        vd, dy.wino_vd, dy = dy.wino_vd, None, dy.g
-        if vd is None:
-            raise _lib.SsvError("wino44_conv2d_dgrad: a LazyGrad without the transformed input the weight gradient leaves")
-    else:
-        vd = dy.__dict__.pop("_wino44_vd", None)
+    if f is _F44:          # the transformed input the weight gradient's one pass over dy already wrote (`wino44_conv2d_wgrad`)
+        if isinstance(dy, LazyGrad):
+            vd, dy.wino_vd, dy = dy.wino_vd, None, dy.g
+            if vd is None:
+                raise _lib.SsvError("wino44_conv2d_dgrad: a LazyGrad without the transformed input the weight gradient leaves")
+        else:
+            vd = dy.__dict__.pop("_wino44_vd", None)
     _lib._dev(dy, w)
     w, wshape = _ohwi(w)
     n, h, w_, k = dy.shape
     c = wshape[1]
-    lib = _lib.load()
-    t = int(lib.ssv_wino44_tiles(n, h, w_))
-    u = _wino44_filter(w, wshape, transposed=True)                # [36][C][K]
-    if vd is not None and tuple(vd.shape) == (36, t, k):
+    t = f.tiles(n, h, w_)
+    u = _wino_filter(w, wshape, transposed=True, form=f)          # [16 | 36][C][K]
+    if vd is not None and tuple(vd.shape) == (f.positions, t, k):
         v = vd
     else:
-        v = torch.empty((36, t, k), dtype=torch.float32, device=dy.device)
-        call("ssv_wino44_input_transform", n, h, w_, k, ptr(dy), None, None, ptr(v), None, stream())
-    m = torch.empty((36, t, c), dtype=torch.float32, device=dy.device)
-    _gemm_batched(36, t, k, c, v, u, m)
+        v = torch.empty((f.positions, t, k), dtype=torch.float32, device=dy.device)
+        call(f.input_transform, n, h, w_, k, ptr(dy), None, None, ptr(v), *((None,) if f is _F44 else ()), stream())
+    m = torch.empty((f.positions, t, c), dtype=torch.float32, device=dy.device)
+    _gemm_batched(f.positions, t, k, c, v, u, m)
     dx = _empty((n, h, w_, c), dy)
     if gate is not None:
-        groups = int(lib.ssv_wino44_groups(n, h, w_, 0))
+        groups = f.groups(n, h, w_, False)
         st, part = _gate_struct(gate, groups, c, dy)
-        call("ssv_wino44_output_transform", n, h, w_, c, ptr(m), ptr(dx), None, None, C.byref(st), stream())
+        call(f.output_transform, n, h, w_, c, ptr(m), ptr(dx), None, None, C.byref(st), stream())
         dx._gate_partials = (part[0], part[1], groups)
     else:
-        call("ssv_wino44_output_transform", n, h, w_, c, ptr(m), ptr(dx), None, None, None, stream())
+        call(f.output_transform, n, h, w_, c, ptr(m), ptr(dx), None, None, None, stream())
     return dx
+
+
+def _wino_wgrad(f, v, dy, w_like, dw, accumulate, dgrad_follows):
+    """The skeleton both forms share: dM = A dY A^T, the batched products dU_p = dM_p^T V_p over the tiles, dw (+)= G^T dU G."""
+    _note(f.note_wgrad)
+    lazy = dy if isinstance(dy, LazyGrad) else None
+    g = lazy.g if lazy is not None else dy
+    _lib._dev(v, g, dw)
+    _, wshape = _ohwi(w_like)
+    n, h, w_, k = dy.shape
+    c = wshape[1]
+    t = f.tiles(n, h, w_)
+    if f is _F22:
+        dm = torch.empty((16, t, k), dtype=torch.float32, device=g.device)
+        call("ssv_wino_dy_transform", n, h, w_, k, ptr(g), ptr(dm), stream())
+        flush = chunk = 0
+    else:
+        if tuple(v.shape) != (36, t, c):
+            raise _lib.SsvError(f"wino44_conv2d_wgrad: transformed input {tuple(v.shape)} does not belong to a {n}x{h}x{w_}x{c} activation")
+        dm = torch.empty((36, t, k), dtype=torch.float32, device=g.device)
+        # the data gradient of the same layer follows (nn.conv: weight gradient first): when it will run F(4x4) too, its transformed input comes out of this pass
+        both = WINOGRAD44_DY_BOTH and (lazy is not None or (dgrad_follows is not False and _use_wino44(n, h, w_, c, k, WINOGRAD44_MAX_RATIO_DGRAD)))
+        if lazy is not None and not both:
+            raise _lib.SsvError("wino44_conv2d_wgrad: a LazyGrad needs the one-pass transform (ops.WINOGRAD44_DY_BOTH was switched off after the forward marked this layer)")
+        if both:
+            vd = torch.empty((36, t, k), dtype=torch.float32, device=g.device)
+            dyin = _dyin_struct(lazy, 0, n) if lazy is not None else None
+            _note("wino44_dy_both_formed_on_load" if lazy is not None else "wino44_dy_both")
+            call("ssv_wino44_dy_transform_both", n, h, w_, k, ptr(g), None if dyin is None else C.byref(dyin), ptr(vd), ptr(dm), stream())
+            if lazy is not None:
+                lazy.wino_vd = vd
+            else:
+                dy._wino44_vd = vd
+        else:
+            call("ssv_wino44_dy_transform", n, h, w_, k, ptr(g), ptr(dm), stream())
+        # the bf16 instruction folds 32 products per accumulator rounding (the fp32 one: 2), so a chain's rounding error is that of one 16x shorter: the register-level
+        # flush is not needed for the 2e-6 bar (tests/test_gpu_winograd44.py measures it), the chunked fp64 fold stays
+        chunk, flush = WINOGRAD44_WGRAD_CHUNK, (WINOGRAD44_WGRAD_FLUSH_BF16X3 if ARITHMETIC == "bf16x3" else WINOGRAD44_WGRAD_FLUSH)
+    du = torch.empty((f.positions, k, c), dtype=torch.float32, device=g.device)
+    _gemm_batched_wgrad(f.positions, t, c, k, v, dm, du, chunk, flush)
+    call(f.filter_grad, k, c, ptr(du), ptr(dw), int(accumulate), stream())
+    return dw
 
 
 def wino_conv2d_fwd(x, w, in_affine=None, want_stats=False, keep_v=False):
@@ -1821,27 +1864,15 @@ def wino_conv2d_fwd(x, w, in_affine=None, want_stats=False, keep_v=False):
     partials are one per 16 tiles = 64 output rows (needs even H, W); V is the transformed input, kept for the weight gradient."""
     if _use_wino44(x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[0], WINOGRAD44_MAX_RATIO_FWD_NO_V2 if WINOGRAD44_WGRAD else WINOGRAD44_MAX_RATIO_FWD):
         return wino44_conv2d_fwd(x, w, in_affine, want_stats, keep_v)
-    _note("wino22_fwd")
-    _lib._dev(x, w)
-    w, wshape = _ohwi(w)
-    n, h, w_, c = x.shape
-    k = wshape[0]
-    lib = _lib.load()
-    t = int(lib.ssv_wino_tiles(n, h, w_))
-    u = _wino_filter(w, wshape)
-    sc, sh = in_affine if in_affine is not None else (None, None)
-    v = torch.empty((16, t, c), dtype=torch.float32, device=x.device)
-    call("ssv_wino_input_transform", n, h, w_, c, ptr(x), ptr(sc), ptr(sh), ptr(v), stream())
-    m = torch.empty((16, t, k), dtype=torch.float32, device=x.device)
-    _gemm_batched(16, t, c, k, v, u, m)
-    y = _empty((n, h, w_, k), x)
-    part = None
-    if want_stats:
-        groups = int(lib.ssv_wino_groups(n, h, w_))
-        part = _empty((2, groups, k), x)
-    call("ssv_wino_output_transform", n, h, w_, k, ptr(m), ptr(y), None if part is None else ptr(part[0]), None if part is None else ptr(part[1]), None, stream())
-    rpg = int(lib.ssv_wino_stats_rows_per_group(n, h, w_)) if want_stats else 0
-    return y, (None if part is None else (part[0], part[1], rpg)), (v if keep_v else None)
+    return _wino_fwd(_F22, x, w, in_affine, want_stats, keep_v)
+
+
+def wino44_conv2d_fwd(x, w, in_affine=None, want_stats=False, keep_v=False):
+    """wino_conv2d_fwd through F(4x4, 3x3): 36 transformed-domain GEMMs over a quarter of the tiles.  ``keep_v``: the weight gradient's operand comes back as
+    the third result - the transformed input V [36][T][C] itself (WINOGRAD44_WGRAD: the weight gradient runs F(4x4) too), or the F(2x2) transformed input
+    [16][T2][C] the input transform then also leaves (wino_conv2d_wgrad tells them apart by the leading dimension).  Statistics partials: one per row of
+    tiles (H % 4 == 0) or per image."""
+    return _wino_fwd(_F44, x, w, in_affine, want_stats, keep_v)
 
 
 def wino_conv2d_dgrad(dy, w, gate=None):
@@ -1849,87 +1880,25 @@ def wino_conv2d_dgrad(dy, w, gate=None):
     a second target): dx is gated and its partial sums come back as ``dx._gate_partials`` like conv2d_dgrad's."""
     if _use_wino44(dy.shape[0], dy.shape[1], dy.shape[2], w.shape[1], dy.shape[3], WINOGRAD44_MAX_RATIO_DGRAD):
         return wino44_conv2d_dgrad(dy, w, gate)
-    _note("wino22_dgrad")
-    _lib._dev(dy, w)
-    w, wshape = _ohwi(w)
-    n, h, w_, k = dy.shape
-    c = wshape[1]
-    lib = _lib.load()
-    t = int(lib.ssv_wino_tiles(n, h, w_))
-    u = _wino_filter(w, wshape, transposed=True)                  # [16][C][K]
-    v = torch.empty((16, t, k), dtype=torch.float32, device=dy.device)
-    call("ssv_wino_input_transform", n, h, w_, k, ptr(dy), None, None, ptr(v), stream())
-    m = torch.empty((16, t, c), dtype=torch.float32, device=dy.device)
-    _gemm_batched(16, t, k, c, v, u, m)
-    dx = _empty((n, h, w_, c), dy)
-    if gate is not None:
-        groups = int(lib.ssv_wino_groups(n, h, w_))
-        st, part = _gate_struct(gate, groups, c, dy)
-        call("ssv_wino_output_transform", n, h, w_, c, ptr(m), ptr(dx), None, None, C.byref(st), stream())
-        dx._gate_partials = (part[0], part[1], groups)
-    else:
-        call("ssv_wino_output_transform", n, h, w_, c, ptr(m), ptr(dx), None, None, None, stream())
-    return dx
+    return _wino_dgrad(_F22, dy, w, gate)
+
+
+def wino44_conv2d_dgrad(dy, w, gate=None):
+    """wino_conv2d_dgrad through F(4x4, 3x3); the gate's partial sums come one per row of tiles.  ``dy`` may be the LazyGrad / tensor whose transformed input
+    the weight gradient's pass already wrote (`wino44_conv2d_wgrad`): the input transform is then skipped."""
+    return _wino_dgrad(_F44, dy, w, gate)
 
 
 def wino_conv2d_wgrad(v, dy, w_like, dw, accumulate=True, dgrad_follows=None):
     """dw (+)= weight gradient of the 3x3 convolution whose transformed input V was kept by wino_conv2d_fwd ([16][T2][C]: F(2x2); [36][T][C]: F(4x4))."""
     if v.shape[0] == 36:
         return wino44_conv2d_wgrad(v, dy, w_like, dw, accumulate, dgrad_follows=dgrad_follows)
-    _note("wino22_wgrad")
-    _lib._dev(v, dy, dw)
-    _, wshape = _ohwi(w_like)
-    n, h, w_, k = dy.shape
-    c = wshape[1]
-    lib = _lib.load()
-    t = int(lib.ssv_wino_tiles(n, h, w_))
-    dm = torch.empty((16, t, k), dtype=torch.float32, device=dy.device)
-    call("ssv_wino_dy_transform", n, h, w_, k, ptr(dy), ptr(dm), stream())
-    du = torch.empty((16, k, c), dtype=torch.float32, device=dy.device)
-    _gemm_batched_wgrad(16, t, c, k, v, dm, du)
-    call("ssv_wino_filter_grad", k, c, ptr(du), ptr(dw), int(accumulate), stream())
-    return dw
+    return _wino_wgrad(_F22, v, dy, w_like, dw, accumulate, dgrad_follows)
 
 
 def wino44_conv2d_wgrad(v, dy, w_like, dw, accumulate=True, dgrad_follows=None):
     """wino_conv2d_wgrad through F(4x4, 3x3): dM = A dY A^T, 36 products dU_p = dM_p^T V_p over the tiles, dw (+)= G^T dU G."""
-    _note("wino44_wgrad")
-    _lib._dev(v, dy.g if isinstance(dy, LazyGrad) else dy, dw)
-    _, wshape = _ohwi(w_like)
-    n, h, w_, k = dy.shape
-    c = wshape[1]
-    lib = _lib.load()
-    t = int(lib.ssv_wino44_tiles(n, h, w_))
-    if tuple(v.shape) != (36, t, c):
-        raise _lib.SsvError(f"wino44_conv2d_wgrad: transformed input {tuple(v.shape)} does not belong to a {n}x{h}x{w_}x{c} activation")
-    lazy = dy if isinstance(dy, LazyGrad) else None
-    g = lazy.g if lazy is not None else dy
-    dm = torch.empty((36, t, k), dtype=torch.float32, device=g.device)
-    # the data gradient of the same layer follows (nn.conv: weight gradient first): when it will run F(4x4) too, its transformed input comes out of this pass
-    both = WINOGRAD44_DY_BOTH and (lazy is not None or (dgrad_follows is not False and _use_wino44(n, h, w_, c, k, WINOGRAD44_MAX_RATIO_DGRAD)))
-    if lazy is not None and not both:
-        raise _lib.SsvError("wino44_conv2d_wgrad: a LazyGrad needs the one-pass transform (ops.WINOGRAD44_DY_BOTH was switched off after the forward marked this layer)")
-    if both:
-        vd = torch.empty((36, t, k), dtype=torch.float32, device=g.device)
-        dyin = _dyin_struct(lazy, 0, n) if lazy is not None else None
-        _note("wino44_dy_both_formed_on_load" if lazy is not None else "wino44_dy_both")
-        call("ssv_wino44_dy_transform_both", n, h, w_, k, ptr(g), None if dyin is None else C.byref(dyin), ptr(vd), ptr(dm), stream())
-        if lazy is not None:
-            lazy.wino_vd = vd
-        else:
-            dy._wino44_vd = vd
-    else:
-        call("ssv_wino44_dy_transform", n, h, w_, k, ptr(g), ptr(dm), stream())
-    dy = g
-    du = torch.empty((36, k, c), dtype=torch.float32, device=dy.device)
-    if ARITHMETIC == "bf16x3":
-        # the bf16 instruction folds 32 products per accumulator rounding (the fp32 one: 2), so a chain's rounding error is that of one 16x shorter: the register-level
-        # flush is not needed for the 2e-6 bar (tests/test_gpu_winograd44.py measures it), the chunked fp64 fold stays
-        _gemm_batched_wgrad(36, t, c, k, v, dm, du, WINOGRAD44_WGRAD_CHUNK, WINOGRAD44_WGRAD_FLUSH_BF16X3)
-    else:
-        _gemm_batched_wgrad(36, t, c, k, v, dm, du, WINOGRAD44_WGRAD_CHUNK, WINOGRAD44_WGRAD_FLUSH)
-    call("ssv_wino44_filter_grad", k, c, ptr(du), ptr(dw), int(accumulate), stream())
-    return dw
+    return _wino_wgrad(_F44, v, dy, w_like, dw, accumulate, dgrad_follows)
 
 
 # ------------------------------------------------------------------------------------------- the 3-channel image stem, row-taps form

@@ -550,30 +550,40 @@ def check_rows(case, name, got, ref64, ref32, fam):
 
 
 # ====================================================================================================================== the runners
-def _run_filt(c, r):
-    inp, r64, r32 = case_refs(c)
+# The four transform kinds run in two parts: _call_<kind> makes every library call of the case on guarded buffers, verifies (d) and the identities (e) and
+# returns the arrays by name (with the library's host answers); _check_<kind> holds them to (a) and (c).  tools/same_bits.py dumps what the first part returns.
+def _call_filt(c, r):
+    inp, _, _ = case_refs(c)
     L, k, ch = r.L, c["K"], c["C"]
     w, prior = r.up(inp["w"]), inp["prior"]
+    o = {}
     for fam, dun in ((F22, "du22"), (F44, "du44")):
         p = wo.POS[fam] ** 2
         du = r.up(inp[dun])
         u, u2 = r.out(f"U{fam}", (p, k, ch)), r.out(f"U{fam}'", (p, k, ch))
-        for o in (u, u2):
-            r.call(PFX[fam] + "filter_transform", k, ch, L.ptr(w), L.ptr(o), L.stream())
+        for t in (u, u2):
+            r.call(PFX[fam] + "filter_transform", k, ch, L.ptr(w), L.ptr(t), L.stream())
         dg, dg2 = r.out(f"dg{fam}", (k, 3, 3, ch)), r.out(f"dg{fam}'", (k, 3, 3, ch))
-        for o in (dg, dg2):
-            r.call(PFX[fam] + "filter_grad", k, ch, L.ptr(du), L.ptr(o), 0, L.stream())
+        for t in (dg, dg2):
+            r.call(PFX[fam] + "filter_grad", k, ch, L.ptr(du), L.ptr(t), 0, L.stream())
         dg0 = r.out(f"dg{fam}_zero", (k, 3, 3, ch), prior=torch.zeros(k, 3, 3, ch))
         dga = r.out(f"dg{fam}_acc", (k, 3, 3, ch), prior=prior)
-        for o in (dg0, dga):
-            r.call(PFX[fam] + "filter_grad", k, ch, L.ptr(du), L.ptr(o), 1, L.stream())
+        for t in (dg0, dga):
+            r.call(PFX[fam] + "filter_grad", k, ch, L.ptr(du), L.ptr(t), 1, L.stream())
         r.same += [(f"second filter_transform {fam}", u, u2), (f"second filter_grad {fam}", dg, dg2), (f"accumulate on zero == overwrite {fam}", dg0, dg)]
-        r.finish()
-        for name, got in ((f"U{fam}", u), (f"dg{fam}", dg), (f"dg{fam}_acc", dga)):
-            check_bar(c, name, got, r64[name][0], r32[name][0], r64[name][1])
+        o.update({f"U{fam}": u, f"dg{fam}": dg, f"dg{fam}_acc": dga})
+    r.finish()
+    return o
+
+
+def _check_filt(c, o):
+    inp, r64, r32 = case_refs(c)
+    for fam in (F22, F44):
+        for name in (f"U{fam}", f"dg{fam}", f"dg{fam}_acc"):
+            check_bar(c, name, o[name], r64[name][0], r32[name][0], r64[name][1])
         # a seeded prior: prior + overwrite within one rounding
-        want = prior.double() + dg.cpu().double()
-        err = (dga.cpu().double() - want).abs()
+        want = inp["prior"].double() + o[f"dg{fam}"].cpu().double()
+        err = (o[f"dg{fam}_acc"].cpu().double() - want).abs()
         assert bool((err <= U * want.abs() + 1e-45).all()), f"{c.id} dg{fam}_acc: {float((err / want.abs().clamp_min(1e-30)).max()) / U:.2f} roundings from prior + overwrite"
 
 
@@ -584,8 +594,8 @@ def _bn_apply_relu(r, x, sc, sh):
     return a
 
 
-def _run_in(c, r):
-    inp, r64, r32 = case_refs(c)
+def _call_in(c, r):
+    inp, _, _ = case_refs(c)
     L, n, h, w, ch = r.L, c["N"], c["H"], c["W"], c["C"]
     lib = L.load()
     t4, t2 = int(lib.ssv_wino44_tiles(n, h, w)), int(lib.ssv_wino_tiles(n, h, w))
@@ -615,19 +625,24 @@ def _run_in(c, r):
                ("fused V2 == fused ssv_wino_input_transform", v2x_b, w_x), ("fused F(4x4) input == transform of ssv_bn_apply's activation", vx_a, vm),
                ("fused F(2x2) input == transform of ssv_bn_apply's activation", w_x, w_m), ("second F(2x2) call", w_p, w_p2), ("second F(4x4) call", v_a, v_a2)]
     r.finish()
-    for name, got in (("V44", v_a), ("V44xf", vx_a), ("V22", w_p), ("V22xf", w_x)):
-        check_bar(c, name, got, r64[name][0], r32[name][0], r64[name][1])
+    return {"V44": v_a, "V44xf": vx_a, "V22": w_p, "V22xf": w_x, "V44+V2": v_b, "V44+V2.V2": v2_b, "V44xf+V2": vx_b, "V44xf+V2.V2": v2x_b, "tiles44": t4, "tiles22": t2}
 
 
-def _run_dy(c, r):
-    inp, r64, r32 = case_refs(c)
+def _check_in(c, o):
+    _, r64, r32 = case_refs(c)
+    for name in ("V44", "V44xf", "V22", "V22xf"):
+        check_bar(c, name, o[name], r64[name][0], r32[name][0], r64[name][1])
+
+
+def _call_dy(c, r):
+    inp, _, _ = case_refs(c)
     L, n, h, w, k = r.L, c["N"], c["H"], c["W"], c["K"]
     lib = L.load()
     t4, t2 = int(lib.ssv_wino44_tiles(n, h, w)), int(lib.ssv_wino_tiles(n, h, w))
     dy, x, coef = r.up(inp["dy"]), r.up(inp["x"]), r.up(inp["coef"])
     dm22, dm22b = r.out("dM22", (16, t2, k)), r.out("dM22'", (16, t2, k))
-    for o in (dm22, dm22b):
-        r.call("ssv_wino_dy_transform", n, h, w, k, L.ptr(dy), L.ptr(o), L.stream())
+    for t in (dm22, dm22b):
+        r.call("ssv_wino_dy_transform", n, h, w, k, L.ptr(dy), L.ptr(t), L.stream())
     dm44 = r.out("dM44", (36, t4, k))
     r.call("ssv_wino44_dy_transform", n, h, w, k, L.ptr(dy), L.ptr(dm44), L.stream())
     vin = torch.empty((36, t4, k), device=r.dev)
@@ -642,8 +657,13 @@ def _run_dy(c, r):
     r.same += [("both: Vd == ssv_wino44_input_transform(dy)", vd, vin), ("both: dM == ssv_wino44_dy_transform(dy)", dmb, dm44), ("second dy_transform", dm22, dm22b),
                ("second dy_transform_both (Vd)", vd, vd2), ("second dy_transform_both (dM)", dmb, dmb2)]
     r.finish()
-    for name, got in (("dM22", dm22), ("dM44", dm44), ("Vd44", vd), ("dM44_dyin", dmf), ("Vd44_dyin", vdf)):
-        check_bar(c, name, got, r64[name][0], r32[name][0], r64[name][1])
+    return {"dM22": dm22, "dM44": dm44, "Vd44": vd, "dM44(both)": dmb, "dM44_dyin": dmf, "Vd44_dyin": vdf, "tiles44": t4, "tiles22": t2}
+
+
+def _check_dy(c, o):
+    _, r64, r32 = case_refs(c)
+    for name in ("dM22", "dM44", "Vd44", "dM44_dyin", "Vd44_dyin"):
+        check_bar(c, name, o[name], r64[name][0], r32[name][0], r64[name][1])
 
 
 def _gate_struct(r, inp, k, groups, mask):
@@ -656,21 +676,20 @@ def _gate_struct(r, inp, k, groups, mask):
     return st, pg, pgx, keep
 
 
-def _run_out(c, r):
-    inp, r64, r32 = case_refs(c)
+def _call_out(c, r):
+    inp, _, _ = case_refs(c)
     L, fam, mode, n, h, w, k = r.L, c["fam"], c["mode"], c["N"], c["H"], c["W"], c["K"]
     lib = L.load()
     entry = PFX[fam] + "output_transform"
     groups = int(lib.ssv_wino_groups(n, h, w)) if fam == F22 else int(lib.ssv_wino44_groups(n, h, w, 1 if mode == "stats" else 0))
     assert groups == wo.groups(fam, n, h, w, mode == "stats")
     m = r.up(inp["M"])
-    fk = FAMKEY[fam]
+    o = {"groups": groups}
     if mode == "plain":
         y, y2 = r.out("y", (n, h, w, k)), r.out("y'", (n, h, w, k))
-        for o in (y, y2):
-            r.call(entry, n, h, w, k, L.ptr(m), L.ptr(o), None, None, None, L.stream())
+        for t in (y, y2):
+            r.call(entry, n, h, w, k, L.ptr(m), L.ptr(t), None, None, None, L.stream())
         r.same.append(("second call", y, y2))
-        r.finish()
     elif mode == "stats":
         rpg = int(lib.ssv_wino_stats_rows_per_group(n, h, w)) if fam == F22 else int(lib.ssv_wino44_stats_rows_per_group(n, h, w))
         assert rpg == wo.stats_rows_per_group(fam, n, h, w) > 0
@@ -681,30 +700,50 @@ def _run_out(c, r):
         r.call(entry, n, h, w, k, L.ptr(m), L.ptr(y2), L.ptr(pmb), L.ptr(pm2b), None, L.stream())
         r.call(entry, n, h, w, k, L.ptr(m), L.ptr(yp), None, None, None, L.stream())
         r.same += [("second call (y)", y, y2), ("second call (pmean)", pm, pmb), ("second call (pm2)", pm2, pm2b), ("y with and without the statistics", y, yp)]
-        r.finish()
-        ycpu = y.cpu()
-        (m64, v64), (m32, v32) = wo.stats_partials(fam, ycpu, torch.float64), wo.stats_partials(fam, ycpu, torch.float32)
-        assert [int(x.numel()) for x in wo.group_rows(fam, n, h, w, True)][:-1] == [rpg] * (groups - 1)
-        check_rows(c, "pmean", pm, m64, m32, fk)
-        check_rows(c, "pm2", pm2, v64, v32, fk)
+        o.update({"pmean": pm, "pm2": pm2, "rows_per_group": rpg})
     else:
         sta, pga, pgxa, keep_a = _gate_struct(r, inp, k, groups, mask=False)
         stm, pgm, pgxm, keep_m = _gate_struct(r, inp, k, groups, mask=True)
         stb, pgb, pgxb, keep_b = _gate_struct(r, inp, k, groups, mask=False)
         y, ym, y2 = r.out("y(affine)", (n, h, w, k)), r.out("y(mask)", (n, h, w, k)), r.out("y(affine)'", (n, h, w, k))
-        for st, o in ((sta, y), (stm, ym), (stb, y2)):
-            r.call(entry, n, h, w, k, L.ptr(m), L.ptr(o), None, None, C.byref(st), L.stream())
+        for st, t in ((sta, y), (stm, ym), (stb, y2)):
+            r.call(entry, n, h, w, k, L.ptr(m), L.ptr(t), None, None, C.byref(st), L.stream())
         r.same += [("mask gate == affine gate (y)", ym, y), ("mask gate == affine gate (psum_g)", pgm, pga), ("mask gate == affine gate (psum_gx)", pgxm, pgxa),
                    ("second call (y)", y, y2), ("second call (psum_g)", pga, pgb), ("second call (psum_gx)", pgxa, pgxb)]
-        r.finish()
+        o.update({"psum_g": pga, "psum_gx": pgxa, "y(mask)": ym, "psum_g(mask)": pgm, "psum_gx(mask)": pgxm})
+    r.finish()
+    o["y"] = y
+    return o
+
+
+def _check_out(c, o):
+    inp, r64, r32 = case_refs(c)
+    fam, mode, n, h, w = c["fam"], c["mode"], c["N"], c["H"], c["W"]
+    fk = FAMKEY[fam]
+    y = o["y"]
+    if mode == "stats":
+        ycpu = y.cpu()
+        (m64, v64), (m32, v32) = wo.stats_partials(fam, ycpu, torch.float64), wo.stats_partials(fam, ycpu, torch.float32)
+        assert [int(x.numel()) for x in wo.group_rows(fam, n, h, w, True)][:-1] == [o["rows_per_group"]] * (o["groups"] - 1)
+        check_rows(c, "pmean", o["pmean"], m64, m32, fk)
+        check_rows(c, "pm2", o["pm2"], v64, v32, fk)
+    elif mode == "gate":
         ones = torch.ones(y.shape, dtype=torch.bool)
         ycpu = y.cpu()
         assert torch.equal(ycpu != 0, inp["bit"] & (ycpu != 0)), f"{c.id}: a gated-off element is not zero"
         _, g64, gx64 = wo.gated(fam, ycpu, ones, inp["gx"], inp["mean"], inp["invstd"], torch.float64)
         _, g32, gx32 = wo.gated(fam, ycpu, ones, inp["gx"], inp["mean"], inp["invstd"], torch.float32)
-        check_rows(c, "psum_g", pga, g64, g32, fk)
-        check_rows(c, "psum_gx", pgxa, gx64, gx32, fk)
+        check_rows(c, "psum_g", o["psum_g"], g64, g32, fk)
+        check_rows(c, "psum_gx", o["psum_gx"], gx64, gx32, fk)
     check_bar(c, "y", y, r64["y"][0], r32["y"][0], r64["y"][1])
+
+
+CALLERS = {"filt": (_call_filt, _check_filt), "in": (_call_in, _check_in), "dy": (_call_dy, _check_dy), "out": (_call_out, _check_out)}
+
+
+def _run_transform(c, r):
+    call, check = CALLERS[c.kind]
+    check(c, call(c, r))
 
 
 def _gemm_check(c, name, got, ref64, amag, arith):
@@ -785,7 +824,7 @@ def _run_wgrad(c, r):
     assert e16 <= GEMM_BF16_BAR * e32 + 1e-9, f"{c.id}: bf16x3 is {e16:.3e} from fp64, fp32 MFMA {e32:.3e} (x{e16 / e32:.3f})"
 
 
-RUNNERS = {"filt": _run_filt, "in": _run_in, "dy": _run_dy, "out": _run_out, "gemm": _run_gemm, "wgrad": _run_wgrad}
+RUNNERS = {"filt": _run_transform, "in": _run_transform, "dy": _run_transform, "out": _run_transform, "gemm": _run_gemm, "wgrad": _run_wgrad}
 
 
 @pytest.mark.gpu

@@ -68,9 +68,13 @@ def launches_by_scope(csrc_dir):
         text = open(f).read()
         for m in re.finditer(r'^(?:extern "C" |static |template <[^\n]*>\n)?[\w:<> \*]+\s+\**(\w+)\([^;{]*\)\s*\{\n(.*?)^\}', text, re.S | re.M):
             body = m.group(2)
-            scopes = [c.lower() for c in re.findall(r"SSV_PROF_(\w+)", " ".join(re.findall(r"ProfScope ps\(([^;]+);", body)))]
-            # SSV_FUSED_LADDER (csrc/bank_softmax.h) launches the kernel template it is handed at every <DT, KT>
-            kernels = [k + (t or "") for k, t in re.findall(r"(?:hipLaunchKernelGGL\(\(?|SSV_FUSED_LADDER\()\s*(\w+)(<[^>]*>)?", body)]
+            # wino_launch_kc (csrc/winograd_tile.h) opens the scope it is handed and launches the kernel it is handed
+            kc = re.findall(r'wino_launch_kc\("\w+", SSV_PROF_(\w+), (\w+)', body)
+            scopes = [c.lower() for c in re.findall(r"SSV_PROF_(\w+)", " ".join(re.findall(r"ProfScope ps\(([^;]+);", body))) + [c for c, _ in kc]]
+            # SSV_FUSED_LADDER (csrc/bank_softmax.h) launches the kernel template it is handed at every <DT, KT>, SSV_WINO_MODE_LADDER (csrc/winograd_tile.h) at
+            # MODE 0 .. 3: <0>, <1> under the forward's scope, <2>, <3> (the gate) under the data gradient's - both scopes are named in the entry point's ProfScope
+            kernels = [k + (t or "") for k, t in re.findall(r"(?:hipLaunchKernelGGL\(\(?|SSV_FUSED_LADDER\()\s*(\w+)(<[^>]*>)?", body)] + [k for _, k in kc]
+            kernels += [f"{k}<{m}>" for k in re.findall(r"SSV_WINO_MODE_LADDER\(\s*(\w+)", body) for m in range(4)]
             if scopes and kernels:
                 out.append((os.path.basename(f), m.group(1), scopes, kernels))
     return out

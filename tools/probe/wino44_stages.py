@@ -36,7 +36,7 @@ for name, H, Cc in (("56x56x64", 56, 64), ("28x28x128", 28, 128), ("14x14x256", 
     gate = ops.BnGateCtx(x, mean, invstd, scale=sc, shift=sh)
     t2, t4 = int(lib.ssv_wino_tiles(B, H, H)), int(lib.ssv_wino44_tiles(B, H, H))
     wt, wsh = ops._ohwi(w)
-    u2, u4 = ops._wino_filter(wt, wsh), ops._wino44_filter(wt, wsh)
+    u2, u4 = ops._wino_filter(wt, wsh), ops._wino_filter(wt, wsh, form=ops._F44)
     v2 = torch.empty(16, t2, Cc, device=dev); m2 = torch.empty(16, t2, Cc, device=dev)
     v4 = torch.empty(36, t4, Cc, device=dev); m4 = torch.empty(36, t4, Cc, device=dev)
     y = torch.empty(B, H, H, Cc, device=dev)

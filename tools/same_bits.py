@@ -3,9 +3,13 @@
 time limit) runs ssv_proto_nce, ssv_queue_nce and ssv_nn_lookup through the guarded C-ABI calls of the forms tests (tests/test_gpu_proto_nce_forms.py,
 tests/test_gpu_dense_nce_forms.py, tests/test_gpu_nn_lookup_forms.py: guards, NaN tails and a prefilled workspace, all verified) in both arithmetics over the
 committed case tables - pcl_oracle.cases() + FORM_CASES, densecl_oracle.cases() + FORM_CASES, nnclr_oracle.LOOKUP_CASES + FORM_LOOKUP_CASES - and dumps loss, lse,
-dq and flag (the lookup: idx, sim, nn).  The dumps are compared byte for byte; there is no tolerance.
-    python tools/same_bits.py OLD_LIB NEW_LIB [-o report.json]
-Exit status 1 if a case differs; the first child that does not exit 0 ends the run with status 2."""
+dq and flag (the lookup: idx, sim, nn).  The Winograd stages: every `filt`, `in`, `dy` and `out` case of tests/test_gpu_wino_forms.CASES through the calling half of
+that file's runners (the same guarded buffers, guards and identities verified), every array they return dumped - U, dw, V, V2, dM, Vd, y, both partial pairs - with
+the library's host answers.  The dumps are compared byte for byte; there is no tolerance.
+    python tools/same_bits.py OLD_LIB NEW_LIB [-o report.json] [--old-root DIR]
+--old-root DIR: the old library's child imports the package from DIR (a checkout of the parent commit), the new library's from this tree, and both also run the
+chain table below through ops.wino_conv2d_fwd / _dgrad / _wgrad under ops.large_batch_dispatch() in both arithmetics: a rewrite of the Python drivers is compared
+like a rewrite of the kernels.  Exit status 1 if a case differs; the first child that does not exit 0 ends the run with status 2."""
 import argparse
 import json
 import os
@@ -13,15 +17,74 @@ import subprocess
 import sys
 import tempfile
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+# the package comes from SSV_SAME_BITS_ROOT (the old library's child under --old-root) or from this tree; the case tables and guarded runners always from this tree
+sys.path[:0] = [os.environ.get("SSV_SAME_BITS_ROOT") or ROOT, os.path.join(ROOT, "tests")]
 CHILD_SECONDS = 480
 ARITHS = ("bf16x3", "f32")
+# the chain table: maps (6x6 has ratio 1.0 and stays on F(2x2) with F(4x4) on; 7x7 and 8x8 take F(4x4)), (N, C, K), and the switch that is off (None: the defaults)
+CHAIN_MAPS, CHAIN_NCK = ((6, 6), (7, 7), (8, 8)), ((3, 32, 64), (2, 64, 32), (2, 128, 128))
+CHAIN_OFF = (None, "WINOGRAD44", "WINOGRAD44_WGRAD", "WINOGRAD44_DY_BOTH")
 
 
-def dump(path):
+def chains(ops, dev, arith, out):
+    """forward plain / with statistics / with the fused input / keeping V, data gradient plain / affine gate / mask gate, weight gradient overwriting and
+    accumulating, and (defaults only, where the forward kept F(4x4)'s V) one LazyGrad weight gradient followed by its data gradient"""
+    import torch
+    import wino_oracle as wo
+
+    def put(what, name, t):
+        out[f"wino_chain/{arith}/{what}/{name}"] = t.detach().cpu().numpy()
+
+    for off in CHAIN_OFF:
+        prev = getattr(ops, off) if off else None
+        if off:
+            setattr(ops, off, False)
+        try:
+            for (h, w_) in CHAIN_MAPS:
+                for (n, c, k) in CHAIN_NCK:
+                    what = f"{off or 'defaults'}-{n}x{h}x{w_}-C{c}-K{k}"
+                    g = torch.Generator().manual_seed(1000 * h + 10 * c + k)
+                    rn = lambda *s, scale=1.0: (torch.randn(*s, generator=g) * scale).to(dev)          # noqa: E731
+                    x, dy, gx = rn(n, h, w_, c), rn(n, h, w_, k), rn(n, h, w_, c)
+                    w = rn(k, c, 3, 3, scale=(2.0 / (9 * c)) ** 0.5).contiguous(memory_format=torch.channels_last)
+                    sc, sh = (torch.rand(c, generator=g) + 0.5).to(dev), rn(c, scale=0.3)
+                    mean, invstd = rn(c, scale=0.2), (torch.rand(c, generator=g) + 0.5).to(dev)
+                    mask = wo.pack_mask(wo.gate_bit(gx.cpu(), sc.cpu(), sh.cpu())).to(dev)
+                    coef = torch.stack([torch.rand(k, generator=g) + 0.5, torch.randn(k, generator=g) * 0.2, torch.randn(k, generator=g) * 0.3,
+                                        torch.randn(k, generator=g) * 0.1]).to(dev).contiguous()
+                    with ops.large_batch_dispatch() as disp, ops.arithmetic(arith):
+                        put(what, "fwd", ops.wino_conv2d_fwd(x, w)[0])
+                        y, part, _ = ops.wino_conv2d_fwd(x, w, want_stats=True)
+                        put(what, "fwd_stats.y", y), put(what, "fwd_stats.pmean", part[0]), put(what, "fwd_stats.pm2", part[1])
+                        out[f"wino_chain/{arith}/{what}/fwd_stats.rows_per_group"] = np.int64(part[2])
+                        put(what, "fwd_affine", ops.wino_conv2d_fwd(x, w, in_affine=(sc, sh))[0])
+                        y, _, v = ops.wino_conv2d_fwd(x, w, keep_v=True)
+                        put(what, "fwd_keep_v.y", y), put(what, "fwd_keep_v.v", v)
+                        put(what, "dgrad", ops.wino_conv2d_dgrad(dy, w))
+                        for tag, gate in (("affine", ops.BnGateCtx(gx, mean, invstd, scale=sc, shift=sh)), ("mask", ops.BnGateCtx(gx, mean, invstd, mask=mask))):
+                            dx = ops.wino_conv2d_dgrad(dy, w, gate=gate)
+                            put(what, f"dgrad_{tag}.dx", dx), put(what, f"dgrad_{tag}.psum_g", dx._gate_partials[0]), put(what, f"dgrad_{tag}.psum_gx", dx._gate_partials[1])
+                        for acc in (0, 1):
+                            dw = rn(k, c, 3, 3, scale=0.1).contiguous(memory_format=torch.channels_last)
+                            d2 = dy.clone()
+                            ops.wino_conv2d_wgrad(v, d2, w, dw, accumulate=bool(acc))
+                            put(what, f"wgrad_acc{acc}", dw)
+                        put(what, "dgrad_after_wgrad", ops.wino_conv2d_dgrad(d2, w))          # F(4x4): picks up the transformed input the one pass over dy left
+                        if off is None and v.shape[0] == 36:
+                            lazy, dw = ops.LazyGrad(dy, rn(n, h, w_, k), coef), torch.zeros_like(w)
+                            ops.wino_conv2d_wgrad(v, lazy, w, dw, accumulate=False)
+                            put(what, "lazy.wgrad", dw), put(what, "lazy.dgrad", ops.wino_conv2d_dgrad(lazy, w))
+                    out[f"wino_chain/{arith}/{what}/dispatch"] = np.frombuffer(json.dumps(disp.log, sort_keys=True).encode(), dtype=np.uint8)
+        finally:
+            if off:
+                setattr(ops, off, prev)
+
+
+def dump(path, chain):
     """the child: every case in both arithmetics on the library SSV_HIP_LIB names -> one .npz of raw arrays, keyed family/arithmetic/case/output"""
-    import numpy as np
     import torch
     import densecl_oracle as do
     import nnclr_oracle as no
@@ -29,6 +92,7 @@ def dump(path):
     import test_gpu_dense_nce_forms as qn
     import test_gpu_nn_lookup_forms as nn
     import test_gpu_proto_nce_forms as pn
+    import test_gpu_wino_forms as wf
     from ssv_amd import _lib
     assert torch.cuda.is_available(), "same_bits.py runs on the GPU; none is visible"
     lib = _lib.load()
@@ -46,6 +110,15 @@ def dump(path):
             q, b = no.lookup_inputs(name)
             rows, idx, sim = nn._lookup(lib, q, b, c.n, arith, 10.0, nn.FILLS[0], what)
             out.update({f"{what}/nn": rows, f"{what}/idx": idx, f"{what}/sim": sim})
+    dev = torch.device("cuda:0")
+    for case in wf.CASES:
+        if case.kind in wf.CALLERS:
+            for k, v in wf.CALLERS[case.kind][0](case, wf.Run(case, dev)).items():
+                out[f"wino_stage/{case.id}/{k}"] = v.cpu().numpy() if torch.is_tensor(v) else np.int64(v)
+    if chain:
+        from ssv_amd import ops
+        for arith in ARITHS:
+            chains(ops, dev, arith, out)
     np.savez(path, **out)
     print("SHA " + _lib.source_sha16())
 
@@ -55,19 +128,21 @@ def main():
     ap.add_argument("old", nargs="?")
     ap.add_argument("new", nargs="?")
     ap.add_argument("-o", "--out")
+    ap.add_argument("--old-root", help="a checkout of the parent commit: the old library's child imports the package from it, and both children run the chain table")
     ap.add_argument("--dump", help=argparse.SUPPRESS)
+    ap.add_argument("--chain", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.dump:
-        dump(a.dump)
+        dump(a.dump, a.chain)
         return 0
-    import numpy as np
     assert a.old and a.new, "two libraries to compare"
     shas, dumps = {}, {}
     with tempfile.TemporaryDirectory() as tmp:
         for tag, lib in (("parent", a.old), ("new", a.new)):
             path = os.path.join(tmp, tag + ".npz")
             try:
-                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--dump", path], env=dict(os.environ, SSV_HIP_LIB=os.path.abspath(lib)),
+                env = dict(os.environ, SSV_HIP_LIB=os.path.abspath(lib), SSV_SAME_BITS_ROOT=os.path.abspath(a.old_root) if (a.old_root and tag == "parent") else ROOT)
+                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--dump", path] + (["--chain"] if a.old_root else []), env=env,
                                      capture_output=True, text=True, timeout=CHILD_SECONDS)
             except subprocess.TimeoutExpired:
                 sys.stderr.write(f"the child on {lib} ran into its time limit of {CHILD_SECONDS} s: nothing more is run\n")
@@ -92,7 +167,10 @@ def main():
             e.setdefault("differs", []).append(name)
     ok = all(e["identical"] for e in cases.values())
     doc = {"what": "outputs of two builds of the library on the same seeded inputs, each library in a fresh process (selected through SSV_HIP_LIB), through the guarded "
-                   "C-ABI calls of the forms tests in both arithmetics; the dumped arrays (loss, lse, dq, flag; the lookup: idx, sim, nn) are compared byte for byte",
+                   "C-ABI calls of the forms tests in both arithmetics; the dumped arrays (loss, lse, dq, flag; the lookup: idx, sim, nn; the Winograd stages: every "
+                   "array their runners return and the host answers; with --old-root the chain table through ops.wino_conv2d_* with the old child's package taken "
+                   "from the parent's tree: every result, partial, kept V and the dispatch log) are compared byte for byte",
+           "old_root": bool(a.old_root),
            "ssv_source_sha16": shas, "cases_compared": len(cases), "all_identical": ok, "cases": cases}
     if a.out:
         with open(a.out, "w") as fh:
