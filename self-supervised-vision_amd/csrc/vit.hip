@@ -14,112 +14,13 @@
 //   dK/dV pass        : S  = Q K^T, dP = dO V^T (key on the lane), dV^T += dO^T P, dK^T += Q^T dS the same way.
 // The contraction over the head dimension is taken in the order d = 32*half + s, so each lane's operand fragment is 32
 // CONSECUTIVE floats of one row (8 x 16-byte loads).
+// What the five attention kernels share - the wave's coordinates, the staging walk, the double-buffered loop, the products, the softmax step, P and dS, the
+// transposed accumulation and the epilogues - stands once in attention_tile.h.
 #include "common.h"
 #include "split_bf16.h"
+#include "attention_tile.h"
 
 namespace {
-
-constexpr int DH = 64;
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-using splitbf::acc32_row;
-
-// 32 consecutive floats of one row -> registers (optionally scaled)
-__device__ __forceinline__ void load_row32(const float* __restrict__ p, float* __restrict__ r, float scale) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const f32x4 v = *(const f32x4*)(p + 4 * i);
-    r[4 * i + 0] = v[0] * scale; r[4 * i + 1] = v[1] * scale; r[4 * i + 2] = v[2] * scale; r[4 * i + 3] = v[3] * scale;
-  }
-}
-
-// acc^T[d][col] tile stored as rows of a [T][ld] matrix: lane (col, half) owns 4 consecutive d per register quad
-__device__ __forceinline__ void store_tile_T(float* __restrict__ base, int64_t row_stride, int row, bool valid, int half,
-                                             const f32x16& lo, const f32x16& hi, float mul) {
-  if (!valid) return;
-  float* p = base + (int64_t)row * row_stride;
-#pragma unroll
-  for (int jj = 0; jj < 4; ++jj) {
-    f32x4 a, b;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { a[e] = lo[4 * jj + e] * mul; b[e] = hi[4 * jj + e] * mul; }
-    *(f32x4*)(p + 8 * jj + 4 * half) = a;
-    *(f32x4*)(p + 32 + 8 * jj + 4 * half) = b;
-  }
-}
-
-// The same tile through a wave-private 32 x 64 float LDS scratch, so that the global stores are whole 256-byte rows (16 lanes x 16 bytes, four rows per
-// instruction) instead of 64 scattered 16-byte pieces: the scattered form is store-ISSUE bound (~7 B / cycle / CU: round 4's cycle stamps found the 37-token
-// backward spending a quarter of its time issuing dQ stores).  Row c keeps its sixteen 16-byte slots XOR-swizzled with c & 15: the transposing writes and the
-// row-major reads are both free of bank conflicts without padding (the scratch is exactly one tile).  Rows [0, nrows) of the tile are stored.
-__device__ __forceinline__ void store_tile_T_rows(float* __restrict__ scratch, float* __restrict__ base, int64_t row_stride, int row0, int nrows, int lane,
-                                                  const f32x16& lo, const f32x16& hi, float mul) {
-  const int c = lane & 31, half = lane >> 5;
-#pragma unroll
-  for (int jj = 0; jj < 4; ++jj) {
-    f32x4 a, b;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { a[e] = lo[4 * jj + e] * mul; b[e] = hi[4 * jj + e] * mul; }
-    *(f32x4*)(scratch + c * 64 + (((2 * jj + half) ^ (c & 15)) << 2)) = a;
-    *(f32x4*)(scratch + c * 64 + (((8 + 2 * jj + half) ^ (c & 15)) << 2)) = b;
-  }
-  const int s = lane & 15;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int r = 4 * k + (lane >> 4);
-    const f32x4 v = *(const f32x4*)(scratch + r * 64 + ((s ^ (r & 15)) << 2));
-    if (r < nrows) *(f32x4*)(base + (int64_t)(row0 + r) * row_stride + 4 * s) = v;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ attention, shared pieces
-// A workgroup = NW wavefronts = NW consecutive 32-row tiles of ONE (image, head).  The tiles it streams over (keys/values in the
-// forward and dQ passes, queries/dO in the dK/dV pass) are staged once per workgroup into LDS with coalesced 16-byte loads
-// (row stride 68 floats: conflict-free ds_read_b128 of a 32-float row fragment) and double-buffered: the global loads of tile
-// t+1 are in flight while the MFMAs of tile t run.
-// Scores are kept in log2 units (Q is pre-multiplied by scale * log2 e), so every softmax exponential is one v_exp_f32;
-// the saved log-sum-exp stays in natural units (converted on store / load).
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-constexpr int TS = 68;                                        // LDS row stride (floats) of a staged 32 x 64 tile
-
-template <int NW>
-struct Stage {                                                // registers holding one thread's share of two 32x64 tiles
-  static constexpr int N4 = 512 / (NW * 64);                  // float4 per thread per tile
-  f32x4 a[N4], b[N4];
-  __device__ __forceinline__ void load(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, int row0, int T) {
-#pragma unroll
-    for (int i = 0; i < N4; ++i) {
-      const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = (e & 15) * 4;
-      const int64_t row = min(row0 + r, T - 1);
-      a[i] = *(const f32x4*)(A + row * lda + c4);
-      b[i] = *(const f32x4*)(B + row * ldb + c4);
-    }
-  }
-  __device__ __forceinline__ void store(float* __restrict__ sa, float* __restrict__ sb) const {
-#pragma unroll
-    for (int i = 0; i < N4; ++i) {
-      const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = (e & 15) * 4;
-      *(f32x4*)(sa + r * TS + c4) = a[i];
-      *(f32x4*)(sb + r * TS + c4) = b[i];
-    }
-  }
-};
-
-__device__ __forceinline__ void lds_row32(const float* __restrict__ tile, int row, int half, float* __restrict__ r) {
-  const float* p = tile + row * TS + half * 32;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const f32x4 v = *(const f32x4*)(p + 4 * i);
-    r[4 * i] = v[0]; r[4 * i + 1] = v[1]; r[4 * i + 2] = v[2]; r[4 * i + 3] = v[3];
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ attention forward
 template <int NW>
@@ -129,64 +30,29 @@ attn_fwd_k(int T, int heads, const float* __restrict__ Q, const float* __restric
                                                       float* __restrict__ O, int ldo, float* __restrict__ LSE) {
   __shared__ __attribute__((aligned(16))) float skv[4][32 * TS];           // K stages 0, 1 | V stages 0, 1; at the end: one output tile per wave
   float (*sk)[32 * TS] = skv, (*sv)[32 * TS] = skv + 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
-  const int q0 = (blockIdx.x * NW + wave) * 32, h = blockIdx.y, b = blockIdx.z;
-  const bool active = q0 < T;                                 // a trailing wave only helps staging
-  const int64_t tok0 = (int64_t)b * T;
-  const int qrow = min(q0 + c, T - 1);
+  SSV_ATTN_WAVE_TILE(q0, qrow, blockIdx.x * NW + wave, T)
   float qreg[32];
-  load_row32(Q + (tok0 + qrow) * ld + h * DH + half * 32, qreg, scale * LOG2E);
+  row32(head_row(Q, tok0 + qrow, ld, h) + half * 32, qreg, scale * LOG2E);
   f32x16 o_lo = zero16(), o_hi = zero16();
   float m = -INFINITY, l = 0.f;
-  const float* kbase = K + tok0 * ld + h * DH;
-  const float* vbase = V + tok0 * ld + h * DH;
+  const float* kbase = head_row(K, tok0, ld, h);
+  const float* vbase = head_row(V, tok0, ld, h);
   Stage<NW> st;
-  st.load(kbase, ld, vbase, ld, 0, T);
-  st.store(sk[0], sv[0]);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < T; k0 += 32, buf ^= 1) {
-    const bool more = k0 + 32 < T;
-    if (more) st.load(kbase, ld, vbase, ld, k0 + 32, T);
+  auto load = [&st, kbase, vbase, ld, T](int k0) { st.load(kbase, ld, vbase, ld, k0, T); };      // captures by value: by reference this kernel gains 2 instructions
+  auto store = [&st, sk, sv](int stage) { st.store(sk[stage], sv[stage]); };
+  SSV_ATTN_STREAM_BEGIN(T, k0, buf, load, store)
     if (active) {
       float kreg[32];
-      lds_row32(sk[buf], c, half, kreg);
+      row32(sk[buf] + c * TS + half * 32, kreg);
       f32x16 s = zero16();
-#pragma unroll
-      for (int i = 0; i < 32; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kreg[i], qreg[i], s, 0, 0, 0);
-      float mt = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (k0 + acc32_row(j, half) >= T) s[j] = -INFINITY;
-        mt = fmaxf(mt, s[j]);
-      }
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float mn = fmaxf(m, mt);
-      const float alpha = ex2(m - mn);                        // m = -inf on the first tile -> 0
-      float ls = 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { s[j] = ex2(s[j] - mn); ls += s[j]; }
-      ls += __shfl_xor(ls, 32, 64);
-      l = l * alpha + ls;
-      m = mn;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { o_lo[j] *= alpha; o_hi[j] *= alpha; }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (k0 + acc32_row(j, 0) >= T) continue;                   // both keys of this step are padding (wave-uniform): P is 0 there
-        const float* vr = sv[buf] + acc32_row(j, half) * TS;
-        o_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[c], s[j], o_lo, 0, 0, 0);
-        o_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32 + c], s[j], o_hi, 0, 0, 0);
-      }
+      SSV_ATTN_PROD32(s, kreg, , qreg)
+      SSV_ATTN_SOFTMAX_STEP(s, k0, T, half, m, l, o_lo, o_hi)
+      SSV_ATTN_ACC_T(k0, T, SSV_ATTN_ACC_PAIR(sv[buf], , s, o_lo, o_hi))     // padding keys: P is 0 there
     }
-    if (more) st.store(sk[buf ^ 1], sv[buf ^ 1]);
-    __syncthreads();
-  }
-  const bool valid = q0 + c < T;
+  SSV_ATTN_STREAM_END(buf, store)
   // (the loop's last barrier has passed: the four staging buffers are free - 2 x 2 x 32 x 68 floats, of which each wave takes a private 32 x 64 tile)
   static_assert(NW * 2048 <= 4 * 32 * TS, "one output tile per wave in the staging buffers");
-  if (active) store_tile_T_rows(&skv[0][0] + wave * 2048, O + tok0 * ldo + h * DH, ldo, q0, min(32, T - q0), lane, o_lo, o_hi, 1.f / l);
-  if (valid && half == 0) LSE[((int64_t)b * heads + h) * T + q0 + c] = (m + log2f(l)) * LN2;
+  SSV_ATTN_STORE_O_LSE(&skv[0][0], O, ldo, LSE, q0, T, heads, o_lo, o_hi, m, l)
 }
 
 // ------------------------------------------------------------------------------------------------ attention forward, SSV_ARITH_BF16X3 (csrc/split_bf16.h)
@@ -209,31 +75,27 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
   // [stage][K | V][plane][32 keys x 128 B]; at the end: one fp32 output tile per wave (NW x 8 KB <= 48 KB)
   __shared__ __attribute__((aligned(16))) unsigned char skv[2 * 2 * 3 * KVP];
   static_assert(NW * 8192 <= 2 * 2 * 3 * KVP, "one output tile per wave in the staging buffers");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
-  const int q0 = (blockIdx.x * NW + wave) * 32, h = blockIdx.y, b = blockIdx.z;
-  const bool active = q0 < T;
-  const int64_t tok0 = (int64_t)b * T;
-  const int qrow = min(q0 + c, T - 1);
+  SSV_ATTN_WAVE_TILE(q0, qrow, blockIdx.x * NW + wave, T)
   bf16x8 qf[4][3];                                             // slab s: d = 16 s + 8 half + {0..7}
   {
-    const float* qp = Q + (tok0 + qrow) * ld + h * DH + 8 * half;
+    const float* qp = head_row(Q, tok0 + qrow, ld, h) + 8 * half;
     const float sc = scale * LOG2E;
 #pragma unroll
     for (int s = 0; s < 4; ++s) splitbf::split8(*(const f32x4*)(qp + 16 * s) * sc, *(const f32x4*)(qp + 16 * s + 4) * sc, qf[s]);
   }
   f32x16 o_lo = zero16(), o_hi = zero16();
   float m = -INFINITY, l = 0.f;
-  const float* kbase = K + tok0 * ld + h * DH;
-  const float* vbase = V + tok0 * ld + h * DH;
+  const float* kbase = head_row(K, tok0, ld, h);
+  const float* vbase = head_row(V, tok0, ld, h);
   constexpr int N4 = 512 / (NW * 64);
   f32x4 rk[N4], rv[N4];
-  auto load_kv = [&](int row0) {
+  auto load_kv = [&](int row0) {                               // Stage<NW>::load's lines, kept here: through Stage<NW> this kernel gains 7 (NW 2) and 10 (NW 4) instructions
 #pragma unroll
     for (int i = 0; i < N4; ++i) {
-      const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = (e & 15) * 4;
-      const int64_t row = min(row0 + r, T - 1);
-      rk[i] = *(const f32x4*)(kbase + row * ld + c4);
-      rv[i] = *(const f32x4*)(vbase + row * ld + c4);
+      const Walk<NW> e(i);
+      const int64_t row = e.row(row0, T);
+      rk[i] = *(const f32x4*)(kbase + row * ld + e.c4());
+      rv[i] = *(const f32x4*)(vbase + row * ld + e.c4());
     }
   };
   auto store_kv = [&](int stage) {
@@ -241,22 +103,16 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
     unsigned char* vp = kp + 3 * KVP;
 #pragma unroll
     for (int i = 0; i < N4; ++i) {
-      const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = e & 15;          // c4: float4 index within the 64-float row
+      const Walk<NW> e(i);
       u32x2 pk[3], pv[3];
       splitbf::split4(rk[i], pk);
       splitbf::split4(rv[i], pv);
-      const int ko = kplane_off(r, c4 >> 1) + (c4 & 1) * 8, vo = vplane_off(r, c4 >> 1) + (c4 & 1) * 8;
+      const int ko = kplane_off(e.r, e.q >> 1) + (e.q & 1) * 8, vo = vplane_off(e.r, e.q >> 1) + (e.q & 1) * 8;
 #pragma unroll
       for (int q = 0; q < 3; ++q) { *(u32x2*)(kp + q * KVP + ko) = pk[q]; *(u32x2*)(vp + q * KVP + vo) = pv[q]; }
     }
   };
-  load_kv(0);
-  store_kv(0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < T; k0 += 32, buf ^= 1) {
-    const bool more = k0 + 32 < T;
-    if (more) load_kv(k0 + 32);
+  SSV_ATTN_STREAM_BEGIN(T, k0, buf, load_kv, store_kv)
     if (active) {
       const unsigned char* kp = skv + buf * 6 * KVP;
       const unsigned char* vp = kp + 3 * KVP;
@@ -268,23 +124,7 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
         for (int q = 0; q < 3; ++q) kf[q] = *(const bf16x8*)(kp + q * KVP + kplane_off(c, 2 * sl + half));
         splitbf::mma6_32(s, kf, qf[sl]);
       }
-      float mt = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (k0 + acc32_row(j, half) >= T) s[j] = -INFINITY;
-        mt = fmaxf(mt, s[j]);
-      }
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float mn = fmaxf(m, mt);
-      const float alpha = ex2(m - mn);
-      float ls = 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { s[j] = ex2(s[j] - mn); ls += s[j]; }
-      ls += __shfl_xor(ls, 32, 64);
-      l = l * alpha + ls;
-      m = mn;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { o_lo[j] *= alpha; o_hi[j] *= alpha; }
+      SSV_ATTN_SOFTMAX_STEP(s, k0, T, half, m, l, o_lo, o_hi)
       // lane -> its V^T rows: d = 32 hh + 16 ((lane >> 4) & 1) + (lane & 15); the lane's address names key quad row (lane & 15) >> 2, d piece (lane & 3)
       const int jl = lane & 15, qq = jl >> 2, pp = jl & 3, dsel = (lane >> 4) & 1;
       typedef __attribute__((address_space(3))) s16x4* lds_p;
@@ -309,12 +149,8 @@ attn_fwd_sp_k(int T, int heads, const float* __restrict__ Q, const float* __rest
         }
       }
     }
-    if (more) store_kv(buf ^ 1);
-    __syncthreads();
-  }
-  const bool valid = q0 + c < T;
-  if (active) store_tile_T_rows(reinterpret_cast<float*>(skv) + wave * 2048, O + tok0 * ldo + h * DH, ldo, q0, min(32, T - q0), lane, o_lo, o_hi, 1.f / l);
-  if (valid && half == 0) LSE[((int64_t)b * heads + h) * T + q0 + c] = (m + log2f(l)) * LN2;
+  SSV_ATTN_STREAM_END(buf, store_kv)
+  SSV_ATTN_STORE_O_LSE(reinterpret_cast<float*>(skv), O, ldo, LSE, q0, T, heads, o_lo, o_hi, m, l)
 }
 
 // ------------------------------------------------------------------------------------------------ attention backward: dQ (and delta)
@@ -325,17 +161,13 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_dq_k(int T, int heads, const
                                                          const float* __restrict__ LSE, float* __restrict__ DELTA,
                                                          float* __restrict__ dQ, int ldg) {
   __shared__ float sk[2][32 * TS], sv[2][32 * TS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
-  const int q0 = (blockIdx.x * NW + wave) * 32, h = blockIdx.y, b = blockIdx.z;
-  const bool active = q0 < T;
-  const int64_t tok0 = (int64_t)b * T;
-  const int qrow = min(q0 + c, T - 1);
+  SSV_ATTN_WAVE_TILE(q0, qrow, blockIdx.x * NW + wave, T)
   float qreg[32], doreg[32];
-  load_row32(Q + (tok0 + qrow) * ld + h * DH + half * 32, qreg, scale * LOG2E);
-  load_row32(dO + (tok0 + qrow) * ldo + h * DH + half * 32, doreg, 1.f);
+  row32(head_row(Q, tok0 + qrow, ld, h) + half * 32, qreg, scale * LOG2E);
+  row32(head_row(dO, tok0 + qrow, ldo, h) + half * 32, doreg);
   float delta = 0.f;
   {
-    const float* op = O + (tok0 + qrow) * ldo + h * DH + half * 32;
+    const float* op = head_row(O, tok0 + qrow, ldo, h) + half * 32;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const f32x4 v = *(const f32x4*)(op + 4 * i);
@@ -343,47 +175,30 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_dq_k(int T, int heads, const
     }
     delta += __shfl_xor(delta, 32, 64);
   }
-  const int64_t stat = ((int64_t)b * heads + h) * T;
+  const int64_t stat = stat_base(b, heads, h, T);
   const float lse = LSE[stat + qrow] * LOG2E;
   const bool valid = q0 + c < T;
   if (valid && half == 0) DELTA[stat + q0 + c] = delta;
   f32x16 g_lo = zero16(), g_hi = zero16();
-  const float* kbase = K + tok0 * ld + h * DH;
-  const float* vbase = V + tok0 * ld + h * DH;
+  const float* kbase = head_row(K, tok0, ld, h);
+  const float* vbase = head_row(V, tok0, ld, h);
   Stage<NW> st;
-  st.load(kbase, ld, vbase, ld, 0, T);
-  st.store(sk[0], sv[0]);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < T; k0 += 32, buf ^= 1) {
-    const bool more = k0 + 32 < T;
-    if (more) st.load(kbase, ld, vbase, ld, k0 + 32, T);
+  auto load = [&](int k0) { st.load(kbase, ld, vbase, ld, k0, T); };
+  auto store = [&](int stage) { st.store(sk[stage], sv[stage]); };
+  SSV_ATTN_STREAM_BEGIN(T, k0, buf, load, store)
     if (active) {
       float kreg[32];
       f32x16 s = zero16(), dp = zero16();
-      lds_row32(sk[buf], c, half, kreg);
+      row32(sk[buf] + c * TS + half * 32, kreg);
+      SSV_ATTN_PROD32(s, kreg, , qreg)
+      row32(sv[buf] + c * TS + half * 32, kreg);
+      SSV_ATTN_PROD32(dp, kreg, , doreg)
 #pragma unroll
-      for (int i = 0; i < 32; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kreg[i], qreg[i], s, 0, 0, 0);
-      lds_row32(sv[buf], c, half, kreg);
-#pragma unroll
-      for (int i = 0; i < 32; ++i) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(kreg[i], doreg[i], dp, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const float p = (k0 + acc32_row(j, half) < T) ? ex2(s[j] - lse) : 0.f;
-        s[j] = p * (dp[j] - delta);                            // dS^T
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (k0 + acc32_row(j, 0) >= T) continue;                   // padding keys: dS is 0
-        const float* kr = sk[buf] + acc32_row(j, half) * TS;
-        g_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[c], s[j], g_lo, 0, 0, 0);
-        g_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32 + c], s[j], g_hi, 0, 0, 0);
-      }
+      for (int j = 0; j < 16; ++j) SSV_ATTN_P_DS(s, dp, j, k0 + acc32_row(j, half) < T, lse, delta)      // dS^T
+      SSV_ATTN_ACC_T(k0, T, SSV_ATTN_ACC_PAIR(sk[buf], , dp, g_lo, g_hi))                               // padding keys: dS is 0
     }
-    if (more) st.store(sk[buf ^ 1], sv[buf ^ 1]);
-    __syncthreads();
-  }
-  store_tile_T(dQ + tok0 * ldg + h * DH, ldg, q0 + c, valid, half, g_lo, g_hi, scale);
+  SSV_ATTN_STREAM_END(buf, store)
+  store_tile_T(head_row(dQ, tok0, ldg, h), ldg, q0 + c, valid, half, g_lo, g_hi, scale);
 }
 
 // ------------------------------------------------------------------------------------------------ attention backward: dK, dV
@@ -393,68 +208,43 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
                                                           const float* __restrict__ dO, int ldo, const float* __restrict__ LSE,
                                                           const float* __restrict__ DELTA, float* __restrict__ dK, float* __restrict__ dV, int ldg) {
   __shared__ float sq[2][32 * TS], sd[2][32 * TS], sstat[2][2][32];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
-  const int k0 = (blockIdx.x * NW + wave) * 32, h = blockIdx.y, b = blockIdx.z;
-  const bool active = k0 < T;
-  const int64_t tok0 = (int64_t)b * T;
-  const int krow = min(k0 + c, T - 1);
+  SSV_ATTN_WAVE_TILE(k0, krow, blockIdx.x * NW + wave, T)            // its tile: keys
   const bool kvalid = k0 + c < T;
   float kreg[32], vreg[32];
-  load_row32(K + (tok0 + krow) * ld + h * DH + half * 32, kreg, 1.f);
-  load_row32(V + (tok0 + krow) * ld + h * DH + half * 32, vreg, 1.f);
-  const int64_t stat = ((int64_t)b * heads + h) * T;
+  row32(head_row(K, tok0 + krow, ld, h) + half * 32, kreg);
+  row32(head_row(V, tok0 + krow, ld, h) + half * 32, vreg);
+  const int64_t stat = stat_base(b, heads, h, T);
   f32x16 dk_lo = zero16(), dk_hi = zero16(), dv_lo = zero16(), dv_hi = zero16();
-  const float* qbase = Q + tok0 * ld + h * DH;
-  const float* dobase = dO + tok0 * ldo + h * DH;
+  const float* qbase = head_row(Q, tok0, ld, h);
+  const float* dobase = head_row(dO, tok0, ldo, h);
   Stage<NW> st;
   float st_stat = 0.f;                                        // threads 0..31: lse, 32..63: delta of the staged query rows
   auto load_stat = [&](int q0) {
     if (threadIdx.x < 64) st_stat = (threadIdx.x < 32 ? LSE : DELTA)[stat + min(q0 + (int)(threadIdx.x & 31), T - 1)] * (threadIdx.x < 32 ? LOG2E : 1.f);
   };
-  st.load(qbase, ld, dobase, ldo, 0, T);
-  load_stat(0);
-  st.store(sq[0], sd[0]);
-  if (threadIdx.x < 64) sstat[0][threadIdx.x >> 5][threadIdx.x & 31] = st_stat;
-  __syncthreads();
-  int buf = 0;
-  for (int q0 = 0; q0 < T; q0 += 32, buf ^= 1) {
-    const bool more = q0 + 32 < T;
-    if (more) { st.load(qbase, ld, dobase, ldo, q0 + 32, T); load_stat(q0 + 32); }
+  auto load = [&](int q0) { st.load(qbase, ld, dobase, ldo, q0, T); load_stat(q0); };
+  auto store = [&](int stage) {
+    st.store(sq[stage], sd[stage]);
+    if (threadIdx.x < 64) sstat[stage][threadIdx.x >> 5][threadIdx.x & 31] = st_stat;
+  };
+  SSV_ATTN_STREAM_BEGIN(T, q0, buf, load, store)
     if (active) {
       float qreg[32];
       f32x16 s = zero16(), dp = zero16();
-      lds_row32(sq[buf], c, half, qreg);
-#pragma unroll
-      for (int i = 0; i < 32; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(qreg[i] * (scale * LOG2E), kreg[i], s, 0, 0, 0);   // rows = query, col = key
-      lds_row32(sd[buf], c, half, qreg);
-#pragma unroll
-      for (int i = 0; i < 32; ++i) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(qreg[i], vreg[i], dp, 0, 0, 0);
+      row32(sq[buf] + c * TS + half * 32, qreg);
+      SSV_ATTN_PROD32(s, qreg, * (scale * LOG2E), kreg)       // rows = query, col = key
+      row32(sd[buf] + c * TS + half * 32, qreg);
+      SSV_ATTN_PROD32(dp, qreg, , vreg)
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int r = acc32_row(j, half);
-        const float p = (q0 + r < T && kvalid) ? ex2(s[j] - sstat[buf][0][r]) : 0.f;
-        s[j] = p;                                              // P
-        dp[j] = p * (dp[j] - sstat[buf][1][r]);                // dS
+        SSV_ATTN_P_DS(s, dp, j, q0 + r < T && kvalid, sstat[buf][0][r], sstat[buf][1][r])
       }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (q0 + acc32_row(j, 0) >= T) continue;                   // padding queries: P and dS are 0
-        const float* qr = sq[buf] + acc32_row(j, half) * TS;
-        const float* dr = sd[buf] + acc32_row(j, half) * TS;
-        dv_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[c], s[j], dv_lo, 0, 0, 0);
-        dv_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[32 + c], s[j], dv_hi, 0, 0, 0);
-        dk_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[c], dp[j], dk_lo, 0, 0, 0);
-        dk_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[32 + c], dp[j], dk_hi, 0, 0, 0);
-      }
+      SSV_ATTN_ACC_T(q0, T, SSV_ATTN_ACC_PAIR(sd[buf], , s, dv_lo, dv_hi) SSV_ATTN_ACC_PAIR(sq[buf], , dp, dk_lo, dk_hi))      // padding queries: P and dS are 0
     }
-    if (more) {
-      st.store(sq[buf ^ 1], sd[buf ^ 1]);
-      if (threadIdx.x < 64) sstat[buf ^ 1][threadIdx.x >> 5][threadIdx.x & 31] = st_stat;
-    }
-    __syncthreads();
-  }
-  store_tile_T(dK + tok0 * ldg + h * DH, ldg, k0 + c, kvalid && active, half, dk_lo, dk_hi, scale);
-  store_tile_T(dV + tok0 * ldg + h * DH, ldg, k0 + c, kvalid && active, half, dv_lo, dv_hi, 1.f);
+  SSV_ATTN_STREAM_END(buf, store)
+  store_tile_T(head_row(dK, tok0, ldg, h), ldg, k0 + c, kvalid && active, half, dk_lo, dk_hi, scale);
+  store_tile_T(head_row(dV, tok0, ldg, h), ldg, k0 + c, kvalid && active, half, dv_lo, dv_hi, 1.f);
 }
 
 // ------------------------------------------------------------------------------------------------ attention backward, ONE pass (T <= 256)
@@ -478,27 +268,22 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
   __shared__ __attribute__((aligned(16))) float sstat[2][32];           // lse (log2 units) | delta of the staged query rows
   __shared__ __attribute__((aligned(16))) float scr[NW][2048];          // per wave: dS^T staging (32 x 36), then its dQ partial (32 registers x 64 lanes)
   constexpr int N4 = 512 / (NW * 64);                                   // float4 per thread per staged 32 x 64 tile
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, half = lane >> 5;
-  const int h = blockIdx.y, b = blockIdx.z;
-  const int k0 = wave * 32;
-  const bool active = k0 < T;
   const int nact = (T + 31) >> 5;                                       // waves that own keys
-  const int64_t tok0 = (int64_t)b * T;
-  const int krow = min(k0 + c, T - 1);
+  SSV_ATTN_WAVE_TILE(k0, krow, wave, T)                                 // wave w owns keys [32 w, 32 w + 32)
   const bool kvalid = k0 + c < T;
-  const int64_t stat = ((int64_t)b * heads + h) * T;
-  const float* qbase = Q + tok0 * ld + h * DH;
-  const float* kbase = K + tok0 * ld + h * DH;
-  const float* obase = O + tok0 * ldo + h * DH;
-  const float* dobase = dO + tok0 * ldo + h * DH;
+  const int64_t stat = stat_base(b, heads, h, T);
+  const float* qbase = head_row(Q, tok0, ld, h);
+  const float* kbase = head_row(K, tok0, ld, h);
+  const float* obase = head_row(O, tok0, ldo, h);
+  const float* dobase = head_row(dO, tok0, ldo, h);
   // all keys -> LDS (rows past T repeat the last row: their probabilities are forced to 0 below)
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = (e & 15) * 4;
-    *(f32x4*)(sK + r * TS + c4) = *(const f32x4*)(kbase + (int64_t)min(r, T - 1) * ld + c4);
+    const Walk<NW> e(i);
+    *(f32x4*)(sK + e.r * TS + e.c4()) = *(const f32x4*)(kbase + e.row(0, T) * ld + e.c4());
   }
   float vreg[32];
-  load_row32(V + (tok0 + krow) * ld + h * DH + half * 32, vreg, 1.f);
+  row32(head_row(V, tok0 + krow, ld, h) + half * 32, vreg);
   f32x16 dk_lo = zero16(), dk_hi = zero16(), dv_lo = zero16(), dv_hi = zero16();
   // staging of one query tile: Q and dO rows to registers, delta = sum_d O * dO reduced over the 16 lanes that share a row
   // load_tile only ISSUES the loads (nothing in it depends on a loaded value, so the wave does not wait for them there - the round-3 form computed delta inside it
@@ -515,11 +300,11 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
 #pragma unroll
     for (int i = 0; i < N4; ++i) {
       if (i >= ni) break;
-      const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = (e & 15) * 4;
-      const int64_t row = min(q0 + r, T - 1);
-      ra[i] = *(const f32x4*)(qbase + row * ld + c4);
-      rb[i] = *(const f32x4*)(dobase + row * ldo + c4);
-      ro[i] = *(const f32x4*)(obase + row * ldo + c4);
+      const Walk<NW> e(i);
+      const int64_t row = e.row(q0, T);
+      ra[i] = *(const f32x4*)(qbase + row * ld + e.c4());
+      rb[i] = *(const f32x4*)(dobase + row * ldo + e.c4());
+      ro[i] = *(const f32x4*)(obase + row * ldo + e.c4());
       rlse[i] = LSE[stat + row];
     }
   };
@@ -527,14 +312,14 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
 #pragma unroll
     for (int i = 0; i < N4; ++i) {
       if (i >= ni) break;
-      const int e = i * NW * 64 + threadIdx.x, r = e >> 4, c4 = (e & 15) * 4;
-      *(f32x4*)(sq + r * TS + c4) = ra[i];
-      *(f32x4*)(sd + r * TS + c4) = rb[i];
+      const Walk<NW> e(i);
+      *(f32x4*)(sq + e.r * TS + e.c4()) = ra[i];
+      *(f32x4*)(sd + e.r * TS + e.c4()) = rb[i];
       float d = ro[i][0] * rb[i][0] + ro[i][1] * rb[i][1] + ro[i][2] * rb[i][2] + ro[i][3] * rb[i][3];
       d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64); d += __shfl_xor(d, 8, 64);
-      if ((e & 15) == 0) {
-        sstat[0][r] = rlse[i] * LOG2E; sstat[1][r] = d;
-        if (q0 + r < T) DELTA[stat + q0 + r] = d;
+      if (e.q == 0) {
+        sstat[0][e.r] = rlse[i] * LOG2E; sstat[1][e.r] = d;
+        if (q0 + e.r < T) DELTA[stat + q0 + e.r] = d;
       }
     }
   };
@@ -551,35 +336,19 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       f32x16 s = zero16(), dp = zero16();
       {
         float kf[32];
-        lds_row32(sq, c, half, fr);
-        lds_row32(sK + k0 * TS, c, half, kf);
-#pragma unroll
-        for (int i = 0; i < 32; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(fr[i] * (scale * LOG2E), kf[i], s, 0, 0, 0);   // rows = query, col = key
+        row32(sq + c * TS + half * 32, fr);
+        row32(sK + k0 * TS + c * TS + half * 32, kf);
+        SSV_ATTN_PROD32(s, fr, * (scale * LOG2E), kf)        // rows = query, col = key
       }
-      lds_row32(sd, c, half, fr);
-#pragma unroll
-      for (int i = 0; i < 32; ++i) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(fr[i], vreg[i], dp, 0, 0, 0);
+      row32(sd + c * TS + half * 32, fr);
+      SSV_ATTN_PROD32(dp, fr, , vreg)
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {                         // rows 8 jj + 4 half + {0..3}: their statistics are one ds_read_b128 each
         const f32x4 l4 = *(const f32x4*)&sstat[0][8 * jj + 4 * half], d4 = *(const f32x4*)&sstat[1][8 * jj + 4 * half];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int j = 4 * jj + e, r = acc32_row(j, half);
-          const float p = (q0 + r < T && kvalid) ? ex2(s[j] - l4[e]) : 0.f;
-          s[j] = p;                                            // P
-          dp[j] = p * (dp[j] - d4[e]);                         // dS
-        }
+        for (int e = 0; e < 4; ++e) SSV_ATTN_P_DS(s, dp, 4 * jj + e, q0 + acc32_row(4 * jj + e, half) < T && kvalid, l4[e], d4[e])
       }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (q0 + acc32_row(j, 0) >= T) continue;                   // padding queries: P and dS are 0
-        const float* qr = sq + acc32_row(j, half) * TS;
-        const float* dr = sd + acc32_row(j, half) * TS;
-        dv_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[c], s[j], dv_lo, 0, 0, 0);
-        dv_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(dr[32 + c], s[j], dv_hi, 0, 0, 0);
-        dk_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[c], dp[j], dk_lo, 0, 0, 0);
-        dk_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[32 + c], dp[j], dk_hi, 0, 0, 0);
-      }
+      SSV_ATTN_ACC_T(q0, T, SSV_ATTN_ACC_PAIR(sd, , s, dv_lo, dv_hi) SSV_ATTN_ACC_PAIR(sq, , dp, dk_lo, dk_hi))       // padding queries: P and dS are 0
       // dS (query on the register index, key on the lane) -> dS^T (key on the register index, query on the lane) through this wave's scratch
 #pragma unroll
       for (int j = 0; j < 16; ++j) myscr[acc32_row(j, half) * 36 + c] = dp[j];
@@ -590,13 +359,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
         st_[4 * jj] = t[0]; st_[4 * jj + 1] = t[1]; st_[4 * jj + 2] = t[2]; st_[4 * jj + 3] = t[3];
       }
       f32x16 g_lo = zero16(), g_hi = zero16();
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (k0 + acc32_row(j, 0) >= T) continue;                   // both keys of this step are padding (wave-uniform): dS is 0 there
-        const float* kr = sK + (k0 + acc32_row(j, half)) * TS;
-        g_lo = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[c], st_[j], g_lo, 0, 0, 0);
-        g_hi = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32 + c], st_[j], g_hi, 0, 0, 0);
-      }
+      SSV_ATTN_ACC_T(k0, T, SSV_ATTN_ACC_PAIR(sK, k0 +, st_, g_lo, g_hi))                                      // padding keys: dS is 0 there
       // this wave's dQ partial, group-major: group G = registers 4 G' .. 4 G' + 3 of lo (G < 4) / hi, one b128 per lane and group
 #pragma unroll
       for (int G = 0; G < 4; ++G) {                            // slot of (G, lane): G * 64 + (lane ^ d4), d4 = 2 G + half = the 16-byte piece of the query's row
@@ -617,17 +380,18 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW
       const int q = i >> 4, d4 = i & 15;
       const int slot = ((d4 >> 1) * 64 + ((q + 32 * (d4 & 1)) ^ d4)) * 4;
       f32x4 acc = *(const f32x4*)(scr[0] + slot);
-      for (int w = 1; w < nact; ++w) acc += *(const f32x4*)(scr[w] + slot);
+      for (int w_ = 1; w_ < nact; ++w_) acc += *(const f32x4*)(scr[w_] + slot);
       if (q0 + q < T) *(f32x4*)(dQ + (tok0 + q0 + q) * ldg + h * DH + 4 * d4) = acc * scale;
     }
     __syncthreads();
   }
   // (past the loop's last barrier every dQ partial has been read: the wave's scratch takes its dK, then its dV tile - whole rows to global memory)
   if (active) {
-    store_tile_T_rows(myscr, dK + tok0 * ldg + h * DH, ldg, k0, min(32, T - k0), lane, dk_lo, dk_hi, scale);
-    store_tile_T_rows(myscr, dV + tok0 * ldg + h * DH, ldg, k0, min(32, T - k0), lane, dv_lo, dv_hi, 1.f);
+    store_tile_T_rows(myscr, head_row(dK, tok0, ldg, h), ldg, k0, min(32, T - k0), lane, dk_lo, dk_hi, scale);
+    store_tile_T_rows(myscr, head_row(dV, tok0, ldg, h), ldg, k0, min(32, T - k0), lane, dv_lo, dv_hi, 1.f);
   }
 }
+
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
 // One wavefront per row, lane owns columns 4*lane + 256*it, the row held in registers: x is read from memory ONCE (rounds 1-3 walked it three times - mean, variance,
@@ -974,17 +738,10 @@ extern "C" int ssv_attention_bwd(int32_t B, int32_t T, int32_t heads, int32_t dh
     SSV_CHECK_LAUNCH("attn_bwd_fused_k");
     return SSV_OK;
   }
-  if (T <= 64) {
-    const dim3 grid(cdiv(T, 64), heads, B);
-    hipLaunchKernelGGL(attn_bwd_dq_k<2>, grid, dim3(128), 0, s, T, heads, q, k, v, ld, scale, o, dout, ldo, lse, delta, dq, ldg);
-    SSV_CHECK_LAUNCH("attn_bwd_dq_k");
-    hipLaunchKernelGGL(attn_bwd_dkv_k<2>, grid, dim3(128), 0, s, T, heads, q, k, v, ld, scale, dout, ldo, lse, delta, dk, dv, ldg);
-  } else {
-    const dim3 grid(cdiv(T, 128), heads, B);
-    hipLaunchKernelGGL(attn_bwd_dq_k<4>, grid, dim3(256), 0, s, T, heads, q, k, v, ld, scale, o, dout, ldo, lse, delta, dq, ldg);
-    SSV_CHECK_LAUNCH("attn_bwd_dq_k");
-    hipLaunchKernelGGL(attn_bwd_dkv_k<4>, grid, dim3(256), 0, s, T, heads, q, k, v, ld, scale, dout, ldo, lse, delta, dk, dv, ldg);
-  }
+  const dim3 grid(cdiv(T, 128), heads, B);            // T > 256: two passes of four-wave workgroups
+  hipLaunchKernelGGL(attn_bwd_dq_k<4>, grid, dim3(256), 0, s, T, heads, q, k, v, ld, scale, o, dout, ldo, lse, delta, dq, ldg);
+  SSV_CHECK_LAUNCH("attn_bwd_dq_k");
+  hipLaunchKernelGGL(attn_bwd_dkv_k<4>, grid, dim3(256), 0, s, T, heads, q, k, v, ld, scale, dout, ldo, lse, delta, dk, dv, ldg);
   SSV_CHECK_LAUNCH("attn_bwd_dkv_k");
   return SSV_OK;
 }

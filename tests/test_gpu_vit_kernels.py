@@ -38,8 +38,7 @@ this file under SSV_VIT_REPORT=<path>), rounded up to the next power of two and 
 
 The launch selection of vit.hip is restated below (attn_fwd_plan, attn_bwd_plan, ln_plan, embed_vector_route); test_restated_plan_is_the_source's pins the
 thresholds those functions restate to the source text, test_case_shapes_have_the_property_their_label_claims holds every case to the property its
-label names, so a retuned threshold fails here instead of silently hollowing the table out.  The `if (T <= 64)` arm behind the `T <= 256` return of
-ssv_attention_bwd is unreachable (attn_bwd_dq_k<2> / attn_bwd_dkv_k<2> are never launched): it gets no case.
+label names, so a retuned threshold fails here instead of silently hollowing the table out.
 
 Branch labels (label, entry point, what the case reaches) - test_case_table_covers_every_documented_branch keeps CASES honest:
 
@@ -232,6 +231,7 @@ SOURCE_PINS = (                                                          # what 
     r"else hipLaunchKernelGGL\(attn_bwd_fused_k<8>",
     r"hipLaunchKernelGGL\(attn_bwd_dq_k<4>, grid, dim3\(256\)",
     r"hipLaunchKernelGGL\(attn_bwd_dkv_k<4>, grid, dim3\(256\)",
+    r"const dim3 grid\(cdiv\(T, 128\), heads, B\);\s*// T > 256: two passes of four-wave workgroups\n  hipLaunchKernelGGL\(attn_bwd_dq_k<4>",
     r"const bool small_next = NW == 2 && T > 32 && T <= 40;",
     r"constexpr int LNF_R = 2;",
     r"constexpr int LNF_TRIPS = 2;",
@@ -670,11 +670,17 @@ def test_case_table_names_every_entry_point():
 
 
 def test_restated_plan_is_the_source():
-    """GPU-free: every threshold that attn_fwd_plan, attn_bwd_plan, ln_plan and embed_vector_route restate stands in vit.hip as restated."""
-    with open(os.path.join(CSRC, "vit.hip")) as f:
-        src = f.read()
+    """GPU-free: every threshold that attn_fwd_plan, attn_bwd_plan, ln_plan and embed_vector_route restate stands in vit.hip (with the attention pieces of
+    attention_tile.h) as restated; the two-pass backward names only its four-wave kernels."""
+    src = ""
+    for name in ("vit.hip", "attention_tile.h"):
+        with open(os.path.join(CSRC, name)) as f:
+            src += f.read()
     for pin in SOURCE_PINS:
         assert re.search(pin, src), f"vit.hip no longer says {pin!r}: restate the plan in this file and re-derive the case table"
+    assert "attn_bwd_dq_k<2>" not in src and "attn_bwd_dkv_k<2>" not in src, "the two-pass backward has a two-wave form again: attn_bwd_plan restates NW 4 only"
+    assert set(re.findall(r"hipLaunchKernelGGL\(attn_bwd_d(?:q|kv)_k<(\d+)>", src)) == {"4"} and src.count("hipLaunchKernelGGL(attn_bwd_dq_k<") == 1
+    assert src.count("hipLaunchKernelGGL(attn_bwd_dkv_k<") == 1
     assert src.count("hipLaunchKernelGGL(attn_bwd_fused_k<") == 3 and src.count("hipLaunchKernelGGL(ln_fwd_k<") == 3 and src.count("hipLaunchKernelGGL(ln_bwd_k<") == 3
 
 

@@ -5,7 +5,9 @@ tests/test_gpu_dense_nce_forms.py, tests/test_gpu_nn_lookup_forms.py: guards, Na
 committed case tables - pcl_oracle.cases() + FORM_CASES, densecl_oracle.cases() + FORM_CASES, nnclr_oracle.LOOKUP_CASES + FORM_LOOKUP_CASES - and dumps loss, lse,
 dq and flag (the lookup: idx, sim, nn).  The Winograd stages: every `filt`, `in`, `dy` and `out` case of tests/test_gpu_wino_forms.CASES through the calling half of
 that file's runners (the same guarded buffers, guards and identities verified), every array they return dumped - U, dw, V, V2, dM, Vd, y, both partial pairs - with
-the library's host answers.  The dumps are compared byte for byte; there is no tolerance.
+the library's host answers.  Attention: every case of kind afwd, abwd and acomp of tests/test_gpu_vit_kernels.CASES through that file's guarded callers (forward in
+both arithmetics, the backward forms; guards, NaN padding columns and the stated identities verified in both children), every array they return dumped - o_*,
+lse_*, delta, dq, dk, dv and the composed gradients - as attention/<case id>/<name>.  The dumps are compared byte for byte; there is no tolerance.
     python tools/same_bits.py OLD_LIB NEW_LIB [-o report.json] [--old-root DIR]
 --old-root DIR: the old library's child imports the package from DIR (a checkout of the parent commit), the new library's from this tree, and both also run the
 chain table below through ops.wino_conv2d_fwd / _dgrad / _wgrad under ops.large_batch_dispatch() in both arithmetics: a rewrite of the Python drivers is compared
@@ -92,6 +94,7 @@ def dump(path, chain):
     import test_gpu_dense_nce_forms as qn
     import test_gpu_nn_lookup_forms as nn
     import test_gpu_proto_nce_forms as pn
+    import test_gpu_vit_kernels as vk
     import test_gpu_wino_forms as wf
     from ssv_amd import _lib
     assert torch.cuda.is_available(), "same_bits.py runs on the GPU; none is visible"
@@ -115,6 +118,13 @@ def dump(path, chain):
         if case.kind in wf.CALLERS:
             for k, v in wf.CALLERS[case.kind][0](case, wf.Run(case, dev)).items():
                 out[f"wino_stage/{case.id}/{k}"] = v.cpu().numpy() if torch.is_tensor(v) else np.int64(v)
+    for case in vk.CASES:
+        if case.kind in ("afwd", "abwd", "acomp"):
+            ctx = vk.Ctx(dev)
+            got = vk.GPU[case.kind](case, vk.KINDS[case.kind][1](case), ctx)
+            ctx.verify(case.id)
+            for k, v in got.items():
+                out[f"attention/{case.id}/{k}"] = v.detach().cpu().numpy()
     if chain:
         from ssv_amd import ops
         for arith in ARITHS:
@@ -168,7 +178,8 @@ def main():
     ok = all(e["identical"] for e in cases.values())
     doc = {"what": "outputs of two builds of the library on the same seeded inputs, each library in a fresh process (selected through SSV_HIP_LIB), through the guarded "
                    "C-ABI calls of the forms tests in both arithmetics; the dumped arrays (loss, lse, dq, flag; the lookup: idx, sim, nn; the Winograd stages: every "
-                   "array their runners return and the host answers; with --old-root the chain table through ops.wino_conv2d_* with the old child's package taken "
+                   "array their runners return and the host answers; attention: every afwd, abwd and acomp case of tests/test_gpu_vit_kernels.CASES through its "
+                   "guarded callers, every array they return; with --old-root the chain table through ops.wino_conv2d_* with the old child's package taken "
                    "from the parent's tree: every result, partial, kept V and the dispatch log) are compared byte for byte",
            "old_root": bool(a.old_root),
            "ssv_source_sha16": shas, "cases_compared": len(cases), "all_identical": ok, "cases": cases}
