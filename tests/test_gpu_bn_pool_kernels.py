@@ -33,7 +33,8 @@ seeded by the case id, so the GPU-free tests below see exactly what the GPU test
 FACTOR and FLOOR: FACTOR is the worst max(0, e(got) - FLOOR) / e(ref32) (and the same for m) measured per family on an MI355X
 (profiles/bn_pool_kernels_report.json, written by this file under SSV_BNPOOL_REPORT=<path>), rounded up to the next power of two and never above 8.
 
-bn_plan / apply_grid of bn.hip are restated below (bn_plan, apply_grid); test_case_shapes_have_the_property_their_label_claims holds every case to
+bn_plan / apply_grid / merge_plan of csrc/bn_plan.h are restated below; test_restated_plan_is_the_plan_of_bn_plan_h holds the restatement to the C++ (a
+stand-alone host program under ASan + UBSan), and test_case_shapes_have_the_property_their_label_claims holds every case to
 the property its label names, so a retuned plan fails here instead of silently hollowing the table out.
 
 Branch labels (label, entry point, what the case reaches) - test_case_table_covers_every_documented_branch keeps CASES honest:
@@ -98,6 +99,7 @@ import json
 import math
 import os
 import re
+import subprocess
 import zlib
 
 import pytest
@@ -893,6 +895,50 @@ def test_collective_shape_properties():
     assert {c["shape"][1] for c in by("gap.shapes")} == {1, 16, 49, 3136} and quarter[0] < 256 and 256 in quarter and any(q > 256 and q % 256 for q in quarter)
     assert {c["groups"] for c in CASES if c.kind == "group"} >= {1, 2, 32} and {c["acc"] for c in CASES if c.kind == "group"} == {True, False}
     assert all(c["K"] % 32 and c["C"] % 32 for c in CASES if c.kind == "ftrans" and c["K"] == 48) and {c["R"] * c["S"] for c in CASES if c.kind == "ftrans"} == {1, 9, 49}
+
+
+def test_restated_plan_is_the_plan_of_bn_plan_h(tmp_path):
+    """GPU-free: tests/bn_plan_main.cpp + csrc/bn_plan.h compiled as a host program with -fsanitize=address,undefined, run over every (M, C) of CASES, every
+    stem shape at full and pooled resolution and every (groups, cap) the part and bwdp cases reach: bn_plan, apply_grid, ws_floats and merge_plan above (and
+    the pooled extent _stem_plans uses) give the numbers the C++ gives, both workspace layouts end where the workspace ends, and no sanitizer report."""
+    cxx = next((p for p in ("/opt/rocm/lib/llvm/bin/clang++", "/usr/bin/clang++", "/usr/bin/g++") if os.path.exists(p)), "c++")
+    exe = tmp_path / "bn_plan_main"
+    res = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                          os.path.join(ROOT, "tests", "bn_plan_main.cpp"), "-o", str(exe)], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    mcs, merges, pools = set(), set(), set()
+    for c in CASES:
+        if c["M"] and c["C"]:
+            mcs.add((c["M"], c["C"]))
+        if c.kind in ("part", "bwdp"):
+            groups, cap, _ = _partial_merge(c)
+            merges.add((groups, cap))
+        if c.kind == "stem":
+            n, h, w, ch = c["shape"]
+            ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            mcs |= {(n * h * w, ch), (n * ho * wo, ch)}
+            pools.add((h, w, ho, wo))
+    assert len(mcs) >= 30 and len(pools) >= 7 and {merge_plan(*m) is None for m in merges} == {True, False}
+    mcs, merges, pools = sorted(mcs), sorted(merges), sorted(pools)
+    want = []
+    for m, ch in mcs:
+        p, g = bn_plan(m, ch), apply_grid(bn_plan(m, ch), m)
+        want.append(f"plan {m} {ch} -> {p['C4']} {p['CT']} {p['RT']} {p['GY']} {p['rpb']} {p['nblk']} | {g['rpb']} {g['nblk']} | {ws_floats(m, ch)}")
+    for groups, cap in merges:
+        factor, ncoarse = merge_plan(groups, cap) or (0, groups)
+        want.append(f"merge {groups} {cap} -> {factor} {ncoarse}")
+    want += [f"pool {h} {w} -> {ho} {wo}" for h, w, ho, wo in pools]
+    want.append(f"bn plans: {len(mcs)} plans, {len(merges)} merges")
+    queries = tmp_path / "queries.txt"
+    queries.write_text("".join(f"plan {m} {ch}\n" for m, ch in mcs) + "".join(f"merge {g} {cap}\n" for g, cap in merges) + "".join(f"pool {h} {w}\n" for h, w, _, _ in pools))
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    run = subprocess.run([str(exe), str(queries)], capture_output=True, text=True, timeout=300, env=env)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error:" not in run.stderr and "Sanitizer" not in run.stderr, run.stderr[-4000:]
+    got = run.stdout.splitlines()
+    assert len(got) == len(want)
+    for g, w_ in zip(got, want):
+        assert g == w_, f"bn_plan.h says '{g}', the restatement in this file '{w_}'"
 
 
 def _err(x, ref64):

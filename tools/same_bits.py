@@ -7,17 +7,22 @@ dq and flag (the lookup: idx, sim, nn).  The Winograd stages: every `filt`, `in`
 that file's runners (the same guarded buffers, guards and identities verified), every array they return dumped - U, dw, V, V2, dM, Vd, y, both partial pairs - with
 the library's host answers.  Attention: every case of kind afwd, abwd and acomp of tests/test_gpu_vit_kernels.CASES through that file's guarded callers (forward in
 both arithmetics, the backward forms; guards, NaN padding columns and the stated identities verified in both children), every array they return dumped - o_*,
-lse_*, delta, dq, dk, dv and the composed gradients - as attention/<case id>/<name>.  The dumps are compared byte for byte; there is no tolerance.
+lse_*, delta, dq, dk, dv and the composed gradients - as attention/<case id>/<name>.  BatchNorm and pooling: every case of tests/test_gpu_bn_pool_kernels.CASES
+through that file's guarded runners (guards, untouched inputs and the stated bitwise identities verified in both children), every tensor they return dumped as
+bn_pool/<case id>/<name>; an array above 16 MB is recorded as the sha256 of its bytes with its shape and dtype, which compares just as exactly.  The dumps are
+compared byte for byte; there is no tolerance.
     python tools/same_bits.py OLD_LIB NEW_LIB [-o report.json] [--old-root DIR]
 --old-root DIR: the old library's child imports the package from DIR (a checkout of the parent commit), the new library's from this tree, and both also run the
 chain table below through ops.wino_conv2d_fwd / _dgrad / _wgrad under ops.large_batch_dispatch() in both arithmetics: a rewrite of the Python drivers is compared
 like a rewrite of the kernels.  Exit status 1 if a case differs; the first child that does not exit 0 ends the run with status 2."""
 import argparse
+import hashlib
 import json
 import os
 import subprocess
 import sys
 import tempfile
+import time
 
 import numpy as np
 
@@ -25,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the package comes from SSV_SAME_BITS_ROOT (the old library's child under --old-root) or from this tree; the case tables and guarded runners always from this tree
 sys.path[:0] = [os.environ.get("SSV_SAME_BITS_ROOT") or ROOT, os.path.join(ROOT, "tests")]
 CHILD_SECONDS = 480
+BIG_BYTES = 16 << 20                                 # a larger array is dumped as its sha256
 ARITHS = ("bf16x3", "f32")
 # the chain table: maps (6x6 has ratio 1.0 and stays on F(2x2) with F(4x4) on; 7x7 and 8x8 take F(4x4)), (N, C, K), and the switch that is off (None: the defaults)
 CHAIN_MAPS, CHAIN_NCK = ((6, 6), (7, 7), (8, 8)), ((3, 32, 64), (2, 64, 32), (2, 128, 128))
@@ -91,6 +97,7 @@ def dump(path, chain):
     import densecl_oracle as do
     import nnclr_oracle as no
     import pcl_oracle as po
+    import test_gpu_bn_pool_kernels as bp
     import test_gpu_dense_nce_forms as qn
     import test_gpu_nn_lookup_forms as nn
     import test_gpu_proto_nce_forms as pn
@@ -125,6 +132,16 @@ def dump(path, chain):
             ctx.verify(case.id)
             for k, v in got.items():
                 out[f"attention/{case.id}/{k}"] = v.detach().cpu().numpy()
+    for case in bp.CASES:
+        ctx = bp.Ctx(dev)
+        got = bp.GPU[case.kind](case, bp.KINDS[case.kind][1](case), ctx)
+        ctx.verify(case.id)
+        for k, v in got.items():
+            a = v.detach().cpu().numpy()
+            if a.nbytes > BIG_BYTES:
+                a = np.frombuffer(json.dumps({"sha256": hashlib.sha256(a.tobytes()).hexdigest(), "shape": list(a.shape), "dtype": str(a.dtype)}).encode(), dtype=np.uint8)
+            out[f"bn_pool/{case.id}/{k}"] = a
+        del ctx, got
     if chain:
         from ssv_amd import ops
         for arith in ARITHS:
@@ -146,10 +163,11 @@ def main():
         dump(a.dump, a.chain)
         return 0
     assert a.old and a.new, "two libraries to compare"
-    shas, dumps = {}, {}
+    shas, dumps, seconds = {}, {}, {}
     with tempfile.TemporaryDirectory() as tmp:
         for tag, lib in (("parent", a.old), ("new", a.new)):
             path = os.path.join(tmp, tag + ".npz")
+            t0 = time.time()
             try:
                 env = dict(os.environ, SSV_HIP_LIB=os.path.abspath(lib), SSV_SAME_BITS_ROOT=os.path.abspath(a.old_root) if (a.old_root and tag == "parent") else ROOT)
                 res = subprocess.run([sys.executable, os.path.abspath(__file__), "--dump", path] + (["--chain"] if a.old_root else []), env=env,
@@ -160,6 +178,7 @@ def main():
             if res.returncode != 0:
                 sys.stderr.write(res.stdout[-2000:] + res.stderr[-4000:] + f"\nthe child on {lib} failed (rc {res.returncode}): nothing more is run\n")
                 return 2
+            seconds[tag] = round(time.time() - t0, 1)
             shas[tag] = [ln for ln in res.stdout.splitlines() if ln.startswith("SHA ")][-1][4:]
             with np.load(path) as z:
                 dumps[tag] = {k: z[k] for k in z.files}
@@ -179,10 +198,11 @@ def main():
     doc = {"what": "outputs of two builds of the library on the same seeded inputs, each library in a fresh process (selected through SSV_HIP_LIB), through the guarded "
                    "C-ABI calls of the forms tests in both arithmetics; the dumped arrays (loss, lse, dq, flag; the lookup: idx, sim, nn; the Winograd stages: every "
                    "array their runners return and the host answers; attention: every afwd, abwd and acomp case of tests/test_gpu_vit_kernels.CASES through its "
-                   "guarded callers, every array they return; with --old-root the chain table through ops.wino_conv2d_* with the old child's package taken "
+                   "guarded callers, every array they return; BatchNorm and pooling: every case of tests/test_gpu_bn_pool_kernels.CASES through its guarded "
+                   "runners, every tensor they return (above 16 MB: its sha256, shape and dtype); with --old-root the chain table through ops.wino_conv2d_* with the old child's package taken "
                    "from the parent's tree: every result, partial, kept V and the dispatch log) are compared byte for byte",
            "old_root": bool(a.old_root),
-           "ssv_source_sha16": shas, "cases_compared": len(cases), "all_identical": ok, "cases": cases}
+           "ssv_source_sha16": shas, "child_seconds": seconds, "child_time_limit": CHILD_SECONDS, "cases_compared": len(cases), "all_identical": ok, "cases": cases}
     if a.out:
         with open(a.out, "w") as fh:
             json.dump(doc, fh, indent=1)
@@ -190,7 +210,7 @@ def main():
     for case, e in cases.items():
         if not e["identical"]:
             print(f"DIFFERENT {case}: {e['differs']}")
-    print(f"{len(cases)} cases, {sum(e['identical'] for e in cases.values())} identical; parent {shas['parent']}, new {shas['new']}")
+    print(f"{len(cases)} cases, {sum(e['identical'] for e in cases.values())} identical; parent {shas['parent']} ({seconds['parent']} s), new {shas['new']} ({seconds['new']} s)")
     return 0 if ok else 1
 
 
